@@ -2,6 +2,7 @@
 """Headline benchmark: env-steps/s of batched FourRooms 11x11 Hansen-4 (BASELINE.json configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs B] [--mode numpy|philox] [--strong]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Workload (per GPU): `MultistoryFourRoomsEnv(B, grid_z=1, obs_type="hansen")` (FR_MAP, cardinal,
@@ -11,9 +12,14 @@ reference's RNG reproduced bit-exactly (rng_mode=numpy, the parity-tested mode) 
 autoreset and obs included. Envs are independent shards: each rank owns its own B envs (weak
 scaling, no data-path collective); RCCL only reduces the timing max and the episode metrics.
 
-Prints ONE JSON line (rank 0) with value = total env-steps / max-over-ranks wall time, the live
-roofline of the step kernel (HIP-event kernel time on its stream) and the CPU baseline (the numpy
-oracle, i.e. the reference's algorithm, timed on this host for a bounded sample).
+Prints ONE JSON line (rank 0) with value = total env-steps / max-over-ranks wall time and ms_per_step
+= that wall time / K. A plain run does only that: set up (the kernel autotune included), W warmup
+steps, the K timed steps, the episode statistics. `--full` adds the legs that take runs of their own:
+the live roofline of the step kernel (HIP-event kernel time on its stream, a separate profiling pass,
+the PMC traffic records and the measured HBM ceilings), the CPU baseline (the numpy oracle, i.e. the
+reference's algorithm, timed on this host for a bounded sample; `--no-cpu-baseline` leaves it out) and,
+with N > 1, the strong-scaling shard. `--dump-outputs DIR` writes the last timed step's outputs
+(DIR/obs.npy, reward.npy, terminated.npy, truncated.npy; see dump_outputs) for comparing two builds.
 """
 import argparse
 import hashlib
@@ -26,8 +32,9 @@ import time
 # The headline's windowed kernel takes a 52-B argument block (a pointer to its device-resident parameters, K and
 # five buffers); the older fused kernels and the C-ROOMS exact-mode draw calls take parameter blocks of ~200-600 B
 # by value, which every wave reads at launch: +1.5-8 µs per launch, by box, where the runtime keeps them in host
-# memory. The package itself leaves the variable alone; an explicit setting wins.
-os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
+# memory. The package itself leaves the variable alone; an explicit setting wins. Set by main(),
+# so that importing this module (tools, tests) changes nothing for the importing process.
+KERNARG_ENV = ("HIP_FORCE_DEV_KERNARG", "1")
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "gym-po-taxi_amd"))
 sys.path.insert(0, ROOT)
@@ -312,6 +319,92 @@ def load_pmc(cfg_key, workload, steps_per_launch, kernel=None):
         f"fit T(K) = {fixed:.4g} + {per_step:.4g}*K bytes over PMC passes at K = {[float(k) for k in ks]}")
 
 
+def roofline_leg(args, W, env, run, B, C, dev, world, rank):
+    """--full: the live roofline of the step kernel, from a profiling pass of its own after the timed region (more
+    launches of the timed region's shape through `run`), the PMC traffic records and, with one rank, the measured
+    HBM ceilings. Returns the line's `roofline` entry."""
+    # live roofline: HIP events bracketing every step-kernel launch on its stream
+    env.set_profiling(True)
+    # whole launches of the timed region's shape (C steps each), so steps_per_launch is exactly C; at least 10
+    # launches (a 3-launch average of 20-step launches moved by ±4% between runs of one build)
+    prof_steps = C * max(10, min(2000 // C, max(args.steps // (2 * C), 1)))
+    run(prof_steps)
+    kms, nk = env.profile_read()
+    rms, nr = env.profile_read_resolver()
+    env.set_profiling(False)
+    kavg_ms = kms / max(nk, 1)
+    ravg_ms = rms / max(nr, 1)
+    steps_per_launch = prof_steps / max(nk, 1)
+    if args.workload != "fourrooms" or steps_per_launch > 1.5:
+        # fused launch of several steps; state read+written once per launch
+        bytes_per_launch = B * (W["bytes"] * steps_per_launch + W["state"])
+        bytes_packed = B * (W["bytes"] * steps_per_launch + W["state_packed"])
+    else:
+        bytes_per_launch = bytes_packed = B * BYTES_PER_ENV_STEP
+    achieved = bytes_per_launch / (kavg_ms * 1e-3) / 1e9
+    achieved_packed = bytes_packed / (kavg_ms * 1e-3) / 1e9
+
+    kernel_name = None
+    if args.workload == "fourrooms" and args.mode == "numpy" and env.query("wgrid"):
+        # launches of up to wgrid_kmax steps run the windowed kernel, longer ones the fused kernel (grid.hip)
+        kernel_name = (f"wgrid_rollout<{env.query('wgrid_block_envs') // 512},{W['n_actions']}>"
+                       if steps_per_launch <= env.query("wgrid_kmax") else "grid_rollout_numpy<GP_OBS_HANSEN,2,4,true>")
+    cfg_key = (f"fourrooms_hansen4_B{B}_{args.mode}" if args.workload == "fourrooms" else
+               f"{args.workload}_B{B}_{args.mode}")
+    kname = W.get("kernel") or (kernel_name if kernel_name else ("grid_rollout_numpy<GP_OBS_HANSEN,2,4,true>"
+                                                             if steps_per_launch > 1.5 else "grid_step_numpy<GP_OBS_HANSEN>")
+                                if args.mode == "numpy" else "grid_rollout_counter<GP_OBS_HANSEN,false>")
+    traffic, traffic_src = load_pmc(cfg_key, args.workload, steps_per_launch, kname)
+    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "byte_model": (f"SURVEY 8(d): {W['bytes']} B per env-step + {W['state']} B per env per launch "
+                               "(canonical state layout)"),
+                "frac_packed_state": achieved_packed / HBM_PEAK_GBS,
+                "bytes_per_launch_packed_state": bytes_packed,
+                "traffic_over_algorithmic": traffic / bytes_per_launch if traffic else None,
+                "traffic_source": traffic_src,
+                "kernel": kname,
+                "steps_per_launch": steps_per_launch,
+                "kernel_avg_us": kavg_ms * 1e3,
+                "bytes_per_launch": bytes_per_launch,
+                "kernel_launches_timed": nk,
+                # the two-kernel path's reset resolver (only launched when neither fused kernel runs)
+                "resolver_kernel": "grid_resolve_numpy<GP_OBS_HANSEN>" if nr else None,
+                "resolver_avg_us": ravg_ms * 1e3 if nr else None}
+    if world == 1 and rank == 0:
+        pk = measured_hbm_peaks(dev)
+        roofline["measured_copy_gbs"] = pk["copy"]
+        roofline["measured_fill_gbs"] = pk["fill"]
+        roofline["frac_of_measured_fill"] = achieved / pk["fill"]
+    return roofline
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per array: 4 arrays x 8 MiB as float32 (obs 16 MiB if float64) stays below 64 MB in all
+
+
+def dump_outputs(dirname, out, k_last):
+    """Write what the last timed step computed, as a caller of the timed rollout receives it: row k_last - 1 of
+    the last launch's (obs, reward, terminated, truncated) buffers, as `dirname`/<name>.npy (float32; float64 for
+    64-bit outputs). An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of its flattened
+    elements (sorted indices from np.random.default_rng(0): the same ones in every run)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, o in zip(("obs", "reward", "terminated", "truncated"), out):
+        row = o[k_last - 1].reshape(-1)
+        if row.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, row.numel(), DUMP_MAX_ELEMS))
+            row = row[torch.as_tensor(idx, device=row.device)]
+        wide = row.dtype in (torch.float64, torch.int64)
+        np.save(os.path.join(dirname, name + ".npy"), row.cpu().numpy().astype(np.float64 if wide else np.float32))
+
+
+def last_launch_steps(steps, C):
+    """Steps of the last launch when `steps` >= 1 timed steps are issued as launches of C steps and one shorter
+    remainder launch: the last timed step is row last_launch_steps - 1 of the output buffers."""
+    return steps - (steps - 1) // C * C
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,14 +416,21 @@ def main():
     ap.add_argument("--strong", action="store_true", help="split --envs across GPUs instead")
     ap.add_argument("--mode", default=None, choices=["numpy", "philox"])
     ap.add_argument("--chunk", type=int, default=None, help="steps per gp_rollout call")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the step kernel's live roofline "
+                         "(profiling pass, PMC records, measured HBM ceilings), the CPU baseline and, with N > 1 "
+                         "GPUs, the strong-scaling shard")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (N > 1: DIR/rank<r>/<name>.npy)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "windowed", "fused"],
                     help="numpy FourRooms: gp_autotune's choice (default) or one kernel for every launch")
     args = ap.parse_args()
+    os.environ.setdefault(*KERNARG_ENV)  # before torch (and with it HIP) loads, below
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # the CPU baseline first, before this process touches the GPU (its worker processes are spawned)
-    cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args.workload)
+    cpu = cpu_baseline(args.workload) if (args.full and not args.no_cpu_baseline and world == 1) else None
 
     import torch
     import torch.distributed as dist
@@ -431,26 +531,11 @@ def main():
     elapsed = time.perf_counter() - t0
     tmax = shard.max_over_ranks(elapsed, dev)
 
-    # live roofline: HIP events bracketing every step-kernel launch on its stream
-    env.set_profiling(True)
-    # whole launches of the timed region's shape (C steps each), so steps_per_launch is exactly C; at least 10
-    # launches (a 3-launch average of 20-step launches moved by ±4% between runs of one build)
-    prof_steps = C * max(10, min(2000 // C, max(args.steps // (2 * C), 1)))
-    run(prof_steps)
-    kms, nk = env.profile_read()
-    rms, nr = env.profile_read_resolver()
-    env.set_profiling(False)
-    kavg_ms = kms / max(nk, 1)
-    ravg_ms = rms / max(nr, 1)
-    steps_per_launch = prof_steps / max(nk, 1)
-    if args.workload != "fourrooms" or steps_per_launch > 1.5:
-        # fused launch of several steps; state read+written once per launch
-        bytes_per_launch = B * (W["bytes"] * steps_per_launch + W["state"])
-        bytes_packed = B * (W["bytes"] * steps_per_launch + W["state_packed"])
-    else:
-        bytes_per_launch = bytes_packed = B * BYTES_PER_ENV_STEP
-    achieved = bytes_per_launch / (kavg_ms * 1e-3) / 1e9
-    achieved_packed = bytes_packed / (kavg_ms * 1e-3) / 1e9
+    if args.dump_outputs and args.steps > 0:  # now: the legs below reuse the output buffers
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"), out,
+                     last_launch_steps(args.steps, C))
+
+    roofline = roofline_leg(args, W, env, run, B, C, dev, world, rank) if args.full else None
 
     m = shard.allreduce_metrics(env.metrics(), dev)  # RCCL: the only collective (episode statistics)
 
@@ -458,7 +543,7 @@ def main():
     # contract's weak-scaling number (1M envs per GPU). With N > 1 each rank also times its strong-scaling
     # shard (2^20 / N envs, same kernel path, same warmup / step counts) and the line carries it.
     strong = None
-    if world > 1 and not args.strong and args.workload == "fourrooms":
+    if args.full and world > 1 and not args.strong and args.workload == "fourrooms":
         Bs = shard.shard_size(args.envs, world, rank, True)
         env_s = W["make"](Bs, dev, args.mode)
         shard.seed_shard(env_s, 0, rank, world)
@@ -494,18 +579,7 @@ def main():
         strong = {"global_envs": args.envs, "envs_per_gpu": Bs, "value": args.envs * args.steps / ts,
                   "ms_per_step": ts / args.steps * 1e3, "scaling": "strong"}
 
-    kernel_name = None
-    if args.workload == "fourrooms" and args.mode == "numpy" and env.query("wgrid"):
-        # launches of up to wgrid_kmax steps run the windowed kernel, longer ones the fused kernel (grid.hip)
-        kernel_name = (f"wgrid_rollout<{env.query('wgrid_block_envs') // 512},{W['n_actions']}>"
-                       if steps_per_launch <= env.query("wgrid_kmax") else "grid_rollout_numpy<GP_OBS_HANSEN,2,4,true>")
     total_steps = (args.envs if args.strong else B * world) * args.steps
-    cfg_key = (f"fourrooms_hansen4_B{B}_{args.mode}" if args.workload == "fourrooms" else
-               f"{args.workload}_B{B}_{args.mode}")
-    kname = W.get("kernel") or (kernel_name if kernel_name else ("grid_rollout_numpy<GP_OBS_HANSEN,2,4,true>"
-                                                             if steps_per_launch > 1.5 else "grid_step_numpy<GP_OBS_HANSEN>")
-                                if args.mode == "numpy" else "grid_rollout_counter<GP_OBS_HANSEN,false>")
-    traffic, traffic_src = load_pmc(cfg_key, args.workload, steps_per_launch, kname)
     line = {
         "metric": W["metric"],
         "value": total_steps / tmax,
@@ -513,6 +587,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": tmax / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "strong" if args.strong else "weak",
@@ -528,22 +603,6 @@ def main():
                    f"forced: {args.kernel}",
                    "pretimed": pretimed, **({"knobs": knobs} if knobs else {}),
                    **({"persistent_grid": persist} if persist else {})},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "byte_model": (f"SURVEY 8(d): {W['bytes']} B per env-step + {W['state']} B per env per launch "
-                                    "(canonical state layout)"),
-                     "frac_packed_state": achieved_packed / HBM_PEAK_GBS,
-                     "bytes_per_launch_packed_state": bytes_packed,
-                     "traffic_over_algorithmic": traffic / bytes_per_launch if traffic else None,
-                     "traffic_source": traffic_src,
-                     "kernel": kname,
-                     "steps_per_launch": steps_per_launch,
-                     "kernel_avg_us": kavg_ms * 1e3,
-                     "bytes_per_launch": bytes_per_launch,
-                     "kernel_launches_timed": nk,
-                     # the two-kernel path's reset resolver (only launched when neither fused kernel runs)
-                     "resolver_kernel": "grid_resolve_numpy<GP_OBS_HANSEN>" if nr else None,
-                     "resolver_avg_us": ravg_ms * 1e3 if nr else None},
         "episodes": {"count": m["episodes"], "mean_return": m["return_sum"] / max(m["episodes"], 1),
                      "mean_length": m["length_sum"] / max(m["episodes"], 1)},
         "lib_hash": lib_hash(),
@@ -551,12 +610,10 @@ def main():
     if strong is not None:
         line["strong"] = strong
     if rank == 0:
-        if world == 1:
-            pk = measured_hbm_peaks(dev)
-            line["roofline"]["measured_copy_gbs"] = pk["copy"]
-            line["roofline"]["measured_fill_gbs"] = pk["fill"]
-            line["roofline"]["frac_of_measured_fill"] = achieved / pk["fill"]
-        line["cpu_baseline"] = cpu
+        if roofline is not None:
+            line["roofline"] = roofline
+        if args.full:
+            line["cpu_baseline"] = cpu
         print(json.dumps(line), flush=True)
     env.close()
     if world > 1:

@@ -1,6 +1,6 @@
 """Attribute the host-side time of bench.py's timed call (VERDICT r2 "next" #3) from a rocprofv3
-`--kernel-trace --hip-runtime-trace` capture of `bench.py --steps 20 --warmup 5` (tools/gpu.sh hiptrace):
-for each fused-kernel launch, host hipLaunchKernel entry -> return, GPU kernel begin -> end, and the
+`--kernel-trace --hip-runtime-trace` capture of `bench.py --full --no-cpu-baseline --steps 20 --warmup 5`
+(tools/gpu.sh hiptrace; with --full the trace also holds the profiling pass and the HBM-ceiling copies): for each fused-kernel launch, host hipLaunchKernel entry -> return, GPU kernel begin -> end, and the
 synchronize that waited for it.
 
     python tools/host_gap.py gpurun_out/hiptrace/out [kernel_substring]

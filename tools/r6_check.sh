@@ -36,7 +36,7 @@ for task in "${@:-tests ab bench floor}"; do
       done ;;
     bench)
       for rep in 1 2; do
-        run 300 $O/bench_$rep.log python3 bench.py --no-cpu-baseline --steps 20 --warmup 5
+        run 300 $O/bench_$rep.log python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5
         tail -n 1 $O/bench_$rep.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print("bench", d["value"], d["ms_per_step"], r["frac"], r["kernel_avg_us"], r["kernel"], d["config"]["kernel_autotune"])'
       done ;;
     stamps)  # phase stamps of the windowed kernel (the GP_STAMPS library, built beforehand on the CPU)
@@ -77,7 +77,7 @@ for task in "${@:-tests ab bench floor}"; do
       for W in ${PW:-crooms anttag taxi}; do
         for rep in 1 2; do
           for bpc in ${PBPC:-0 5 4}; do
-            GP_KNOBS=persist_bpc=$bpc run 300 $O/persist_${W}_$bpc.log python3 bench.py --no-cpu-baseline --workload $W ${PSTEPS:---steps 1024 --warmup 128}
+            GP_KNOBS=persist_bpc=$bpc run 300 $O/persist_${W}_$bpc.log python3 bench.py --full --no-cpu-baseline --workload $W ${PSTEPS:---steps 1024 --warmup 128}
             tail -n 1 $O/persist_${W}_$bpc.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print("'$W' bpc '$bpc'", "%.4g" % d["value"], "us/step %.3f" % (d["ms_per_step"]*1e3), "frac %.3f" % r["frac"], d["config"].get("persistent_grid"))'
           done
         done
@@ -88,7 +88,7 @@ for task in "${@:-tests ab bench floor}"; do
           IFS=: read W V bpc <<< "$c"
           L=$LD/libgympo_amd_$V.so
           [ "$V" = base ] && L=$LD/libgympo_amd.so
-          GYM_PO_AMD_LIB=$L GP_KNOBS=persist_bpc=$bpc run 300 $O/occ_${W}_${V}_$bpc.log python3 bench.py --no-cpu-baseline --workload $W --steps 1024 --warmup 128
+          GYM_PO_AMD_LIB=$L GP_KNOBS=persist_bpc=$bpc run 300 $O/occ_${W}_${V}_$bpc.log python3 bench.py --full --no-cpu-baseline --workload $W --steps 1024 --warmup 128
           tail -n 1 $O/occ_${W}_${V}_$bpc.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print("'$c'", "%.4g" % d["value"], "us/step %.3f" % (d["ms_per_step"]*1e3), "frac %.3f" % r["frac"], d["config"].get("persistent_grid"))'
         done
       done ;;
