@@ -142,6 +142,8 @@ std::unique_ptr<EnvBackend> make_crooms_backend(const gp_crooms_config* cfg, int
                                                 int* err);
 std::unique_ptr<EnvBackend> make_anttag_backend(const gp_anttag_config* cfg, int64_t B, int device, int rng_mode,
                                                 int* err);
+std::unique_ptr<EnvBackend> make_carflag_backend(const gp_carflag_config* cfg, int64_t B, int device, int rng_mode,
+                                                 int* err);
 
 // Small device-buffer owner.
 struct DevBuf {

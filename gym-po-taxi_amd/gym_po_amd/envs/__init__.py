@@ -3,6 +3,8 @@ from .rooms import CRoomsEnv, MultistoryFourRoomsEnv, RoomsEnv
 from .extended_taxi import (EXTENDED_TAXI_MAP, TAXI_MAP, ExtendedHansenTaxiVecEnv, ExtendedTaxiVecEnv,
                             HansenTaxiVecEnv, TaxiVecEnv)
 from .ant_tag_grid import AntTagGridEnv
+from .car_flag import CarVecEnv, DiscreteActionCarVecEnv
 
 __all__ = ["RoomsEnv", "CRoomsEnv", "MultistoryFourRoomsEnv", "TaxiVecEnv", "HansenTaxiVecEnv",
-           "ExtendedTaxiVecEnv", "ExtendedHansenTaxiVecEnv", "TAXI_MAP", "EXTENDED_TAXI_MAP", "AntTagGridEnv"]
+           "ExtendedTaxiVecEnv", "ExtendedHansenTaxiVecEnv", "TAXI_MAP", "EXTENDED_TAXI_MAP", "AntTagGridEnv",
+           "CarVecEnv", "DiscreteActionCarVecEnv"]

@@ -16,6 +16,8 @@
  *   gp_create(GP_KIND_CROOMS) CRoomsEnv.__init__                 gym_po/envs/rooms/crooms.py:104-244
  *   gp_create(GP_KIND_ANTTAG) AntTagEnv task rules (grid restatement, build-defined)
  *                                                                gym_po/envs/ant_tag.py:88-157
+ *   gp_create(GP_KIND_CARFLAG) CarVecEnv.__init__ / DiscreteActionCarVecEnv.__init__
+ *                                                                gym_po/envs/car_flag.py:50-85, :289-299
  *   gp_seed / gp_seed_words   gymnasium Env.reset(seed=) -> seeding.np_random(seed)
  *                             (msrooms.py:376, rooms.py:184, extended_taxi.py:239, crooms.py:246-249)
  *   gp_reset                  *.reset()      msrooms.py:369-381, rooms.py:177-189,
@@ -54,9 +56,10 @@ extern "C" {
 #define GP_KIND_TAXI 2
 #define GP_KIND_CROOMS 3
 #define GP_KIND_ANTTAG 4
+#define GP_KIND_CARFLAG 5 /* Car-Flag: 1-D heaven/hell POMDP (car_flag.py) */
 
 /* ---- RNG modes ---- */
-#define GP_RNG_NUMPY 0   /* seed-identical to numpy Generator(PCG64(SeedSequence(seed))): GRID, CROOMS, TAXI */
+#define GP_RNG_NUMPY 0   /* seed-identical to numpy Generator(PCG64(SeedSequence(seed))): GRID, CROOMS, TAXI, CARFLAG */
 #define GP_RNG_PHILOX 1  /* counter-based Philox4x32-10 keyed by (seed, env, step): fusable rollouts */
 #define GP_RNG_REPLAY 2  /* pre-decided per-env draws supplied by gp_set_replay each step       */
 
@@ -146,6 +149,15 @@ typedef struct gp_anttag_config {
   float tag_reward, step_reward;
 } gp_anttag_config;
 
+/* Car-Flag (car_flag.py:50-144, :286-303). Observation: GP_DTYPE_F32, width 3 (position, velocity, direction). */
+typedef struct gp_carflag_config {
+  int32_t time_limit;      /* truncated = elapsed >= time_limit (car_flag.py:129)                  */
+  int32_t action_kind;     /* 0 = continuous float32 [B] (all-float32 arithmetic); 1 = continuous float64 [B]
+                              (float64 arithmetic, stored as f32); n >= 2 = discrete int32 [B] into action_table
+                              (float64 arithmetic, DiscreteActionCarVecEnv)                          */
+  const double* action_table; /* [n] forces of the discrete actions (np.linspace(-1, 1, n)); else NULL */
+} gp_carflag_config;
+
 typedef struct gp_env gp_env;
 
 const char* gp_last_error(void);
@@ -171,8 +183,9 @@ int gp_get_rng_state(gp_env* env, uint64_t st[6]);
 /* Reset every env (reset()), writing the initial observation to `obs` (device). */
 int gp_reset(gp_env* env, void* obs, void* stream);
 
-/* One batched step with same-step autoreset. actions: int32 [B] (discrete) or float [B,2]
- * (continuous C-ROOMS); obs as gp_obs_info; rew float [B]; term/trunc uint8 [B]. */
+/* One batched step with same-step autoreset. actions: int32 [B] (discrete), float [B,2]
+ * (continuous C-ROOMS) or float32 / float64 [B] (continuous CARFLAG, by its action_kind); obs as
+ * gp_obs_info; rew float [B]; term/trunc uint8 [B]. */
 int gp_step(gp_env* env, const void* actions, void* obs, float* rew, uint8_t* term, uint8_t* trunc,
             void* stream);
 
@@ -192,7 +205,9 @@ void gp_plan_destroy(gp_plan* plan);
 
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
- * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. */
+ * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. CARFLAG: s f32[B,3]
+ * (position, velocity, direction), elapsed i32[B], heavens f32[B] (+-1), priests f32[B] (+-0.5; set takes
+ * both by sign). */
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream);
 int gp_set_state(gp_env* env, const void* a, const void* b, const void* c, const void* d, void* stream);
 
@@ -201,7 +216,9 @@ int gp_set_state(gp_env* env, const void* a, const void* b, const void* c, const
  * int32 [B] (indices into the valid-cell lists). TAXI: reset state int32 [B], passenger/dest
  * pair int32 [B] (p*n_locs+d). CROOMS: action noise f64 [B,2] (the value numpy's
  * normal(scale=action_std) returned), wall noise f64 [B,2] (normal(scale=0.5)), goal/agent index
- * int32 [B] each, uniform k53 uint64 [B] for discrete action failures. */
+ * int32 [B] each, uniform k53 uint64 [B] for discrete action failures. CARFLAG: uniform k53 uint64 [B] of
+ * the reset position (x = -0.2 + 0.4 * k * 2^-53), heaven index int32 [B] into (-1, 1), priest index
+ * int32 [B] into (-0.5, 0.5). */
 int gp_set_replay(gp_env* env, const void* u, const void* i0, const void* i1, const void* f0, const void* f1);
 
 /* Valid-cell lists (host copies) used by the index draws: which = 0 goal, 1 agent. */
