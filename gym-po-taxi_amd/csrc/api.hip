@@ -39,6 +39,9 @@ const char* gp_derr_text(uint32_t flags) {
             sizeof(buf) - strlen(buf) - 1);
   if (flags & GP_DERR_STREAM)
     strncat(buf, "a numpy normal needed more words than one stream window holds; ", sizeof(buf) - strlen(buf) - 1);
+  if (flags & GP_DERR_CTRL)
+    strncat(buf, "a closed-loop rollout met an obs or node outside the controller table (the device clamped it); ",
+            sizeof(buf) - strlen(buf) - 1);
   return buf;
 }
 
@@ -230,6 +233,7 @@ int gp_debug_set(const char* key, int64_t value) {
   else if (!strcmp(key, "xg_ppt_min")) g_dbg.xg_ppt_min = (int)value;
   else if (!strcmp(key, "xg_spb_min")) g_dbg.xg_spb_min = (int)value;
   else if (!strcmp(key, "persist_bpc")) g_dbg.persist_bpc = (int)value;
+  else if (!strcmp(key, "ctrl_lds_max")) g_dbg.ctrl_lds_max = (int)value;
   else if (!strcmp(key, "xg_graph")) gp_xg_graph_knob = (int)value;  // (crooms.hip: read at create)
   else {
     gp_set_error("gp_debug_set: unknown key '%s'", key);
@@ -430,6 +434,27 @@ int gp_plan_run(gp_plan* plan) {
 }
 
 void gp_plan_destroy(gp_plan* plan) { delete plan; }
+
+int gp_set_controller(gp_env* env, int n_nodes, int n_obs, const uint32_t* thr_host) {
+  GP_REQUIRE_ENV();
+  return env->be->set_controller(n_nodes, n_obs, thr_host);
+}
+
+int gp_rollout_controller(gp_env* env, int K, void* obs, int32_t* actions, uint8_t* nodes, float* rew, uint8_t* term,
+                          uint8_t* trunc, void* stream) {
+  GP_REQUIRE_ENV();
+  if (K < 0) {
+    gp_set_error("gp_rollout_controller: bad arguments");
+    return GP_E_INVALID;
+  }
+  if (K == 0) return GP_OK;
+  return env->be->rollout_controller(K, obs, actions, nodes, rew, term, trunc, (hipStream_t)stream);
+}
+
+int gp_controller_nodes(gp_env* env, uint8_t* get, const uint8_t* set, void* stream) {
+  GP_REQUIRE_ENV();
+  return env->be->controller_nodes(get, set, (hipStream_t)stream);
+}
 
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream) {
   GP_REQUIRE_ENV();

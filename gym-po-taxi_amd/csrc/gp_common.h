@@ -142,6 +142,8 @@ GP_HD uint32_t st_count(uint64_t s) { return (uint32_t)s; }
 #define GP_DERR_OVERFLOW 8u // windowed grid kernel slow path: more rejected choice() words than it can list
 #define GP_DERR_BTPE 16u    // Taxi numpy mode: a multinomial reset needed numpy's BTPE binomial (p n > 30) or an
                             // inversion did not end, neither of which the device walker restates
+#define GP_DERR_CTRL 32u    // closed-loop rollout: an obs outside the controller table's n_obs, or a node >= its
+                            // node count (set through gp_controller_nodes): the device clamped it
 // numpy indexing of an n-row table accepts a in [-n, n) (negatives wrap); anything else raises.
 __device__ __forceinline__ bool action_out_of_range(int a, int n) { return (uint32_t)(a + n) >= (uint32_t)(2 * n); }
 __device__ __forceinline__ void flag_bad_action(uint32_t* derr) { atomicOr(derr, GP_DERR_ACTION); }

@@ -43,6 +43,7 @@ struct GpDebugKnobs {
   int wg_block_envs = 0;    // GRID windowed kernel: the smallest envs per block to use (0 = the smallest that fits)
   int wg_fill_simd = 0;     // GRID windowed kernel: per-SIMD window-row deltas, 4 signed nibbles (0 = WG_FILL_SIMD)
   int64_t wg_fill_wave = 0; // GRID windowed kernel: per-wave deltas on top, 8 signed nibbles (wave 0 lowest)
+  int ctrl_lds_max = -1;    // GRID closed-loop rollouts: dynamic LDS bytes per block up to which the controller table is staged in LDS (0 = never; -1 = grid.hip CTRL_LDS_BUDGET); read by gp_set_controller
   int persist_bpc = 0;      // TAXI / CROOMS / ANT-TAG streaming rollouts: blocks per CU (0 = every resident block, persistent_grid)
 };
 const GpDebugKnobs& gp_debug_knobs();
@@ -98,6 +99,20 @@ struct EnvBackend {
   virtual int set_state(const void* a, const void* b, const void* c, const void* d, hipStream_t s) = 0;
   virtual int set_replay(const void* u, const void* i0, const void* i1, const void* f0, const void* f1) {
     gp_set_error("replay mode not supported by this env kind");
+    return GP_E_UNSUPPORTED;
+  }
+  // Closed-loop rollouts (gp_set_controller / gp_rollout_controller / gp_controller_nodes): GRID in philox mode.
+  virtual int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
+    gp_set_error("controllers are not supported by this env kind");
+    return GP_E_UNSUPPORTED;
+  }
+  virtual int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term,
+                                 uint8_t* trunc, hipStream_t s) {
+    gp_set_error("closed-loop rollouts are not supported by this env kind");
+    return GP_E_UNSUPPORTED;
+  }
+  virtual int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) {
+    gp_set_error("controllers are not supported by this env kind");
     return GP_E_UNSUPPORTED;
   }
   virtual int valid_cells(int which, int32_t* out, int cap) const { return 0; }

@@ -2666,6 +2666,140 @@ __global__ __launch_bounds__(TPB) void grid_rollout_counter(GridDev p, int K, ui
   add_metrics(p, rsum, eps, lens, nst);
 }
 
+// ------------------------------------------------------------------ closed-loop rollout ----
+// grid_rollout_counter with the action chosen on the device by a tabular finite-state controller
+// (gp_set_controller; semantics in include/gym_po_amd.h): per env-step one more Philox block, tagged CTRL_TAG,
+// picks j = action * M + next_node from the threshold row of (node, obs), the obs being the scalar obs of the
+// state in registers. The row is read from global memory (L1/L2: ROOMS Hansen-8 tables are 74 KB-4.7 MB, FourRooms
+// Hansen-8 1.9 MB and up), or, CL, from a copy of the table staged in LDS behind the env's tables when both are small
+// (FourRooms Hansen-4: 6.5 KB with M = 1, 26 KB with M = 2). Rows are 16-B aligned: L = nact * M is a multiple of 4.
+constexpr uint32_t CTRL_TAG = 0x67706f63u;  // the env draws carry 0x67706f21 (philox_draws)
+struct CtrlDev {
+  const uint32_t* thr;  // [M][n_obs][L]: nondecreasing rows, entries <= 2^31, last == 2^31 (validated on upload)
+  uint8_t* node;        // [B] the controller node of each env
+  int32_t M, n_obs, L;
+  uint32_t inv_m;       // ceil(2^16 / M): j / M == (j * inv_m) >> 16 for j < 64, M <= 8
+  int32_t lds_off, bytes;  // lds_off >= 0: the table is staged at this offset of the dynamic LDS (CL launches); its size
+};
+// Largest dynamic LDS per block (env tables + controller table) with the controller staged: 5 blocks per CU stay
+// resident, more than the 4 a 2^20-env launch puts there.
+constexpr int CTRL_LDS_BUDGET = 32 * 1024;
+
+__device__ __forceinline__ uint32_t ctrl_count4(const uint4 q, uint32_t y) {
+  return (uint32_t)(y >= q.x) + (uint32_t)(y >= q.y) + (uint32_t)(y >= q.z) + (uint32_t)(y >= q.w);
+}
+// #{i < L : y >= row[i]} for a nondecreasing row whose last entry exceeds y (y < 2^31). Up to 16 entries: every
+// 16-B quad is loaded (independent loads, one latency) and counted. Longer rows: a branch-free binary search over
+// the quads' last entries for the first quad not entirely <= y (never past the last quad), then that quad's count.
+__device__ __forceinline__ uint32_t ctrl_search(const uint32_t* __restrict__ row, int L, uint32_t y) {
+  const uint4* q4 = reinterpret_cast<const uint4*>(row);
+  const int nq = L >> 2;
+  if (nq <= 4) {
+    uint32_t j = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q < nq) j += ctrl_count4(q4[q], y);
+    return j;
+  }
+  int base = 0, len = nq;  // the number of full quads lies in [base, base + len - 1]
+  while (len > 1) {
+    const int half = len >> 1;
+    base = (y >= row[4 * (base + half - 1) + 3]) ? base + half : base;
+    len -= half;
+  }
+  return 4u * (uint32_t)base + ctrl_count4(q4[base], y);
+}
+
+template <int OK, bool LT = false, bool CL = false>
+__global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDev c, int K, uint64_t step0,
+                                                               int32_t* __restrict__ obs, int32_t* __restrict__ act,
+                                                               uint8_t* __restrict__ nodes, float* __restrict__ rew,
+                                                               uint8_t* __restrict__ term,
+                                                               uint8_t* __restrict__ trunc) {
+  static_assert(OK == GP_OBS_HANSEN || OK == GP_OBS_TABLE, "the controller conditions on a scalar obs");
+  __shared__ uint64_t s_thr[64];
+  extern __shared__ __attribute__((aligned(16))) char dyn[];
+  if (threadIdx.x < p.nact * p.nact) s_thr[threadIdx.x] = p.thr[threadIdx.x];
+  if constexpr (LT) lds_image_copy(dyn, p.limg, p.lds.jt.off);  // all but the PCG jump tables (last)
+  if constexpr (CL) lds_image_copy(dyn + c.lds_off, reinterpret_cast<const char*>(c.thr), c.bytes);
+  __syncthreads();
+  const uint32_t* cthr = CL ? reinterpret_cast<const uint32_t*>(dyn + c.lds_off) : c.thr;
+  const auto tb = make_tabs<LT>(p, dyn);
+  const int env0 = blockIdx.x * EPB + threadIdx.x * EPT;
+  uint32_t ae4[4];
+  load4<uint32_t>(p.ae, env0, p.B, ae4);
+  int g4[4];
+  if (p.fixed_goal < 0) {
+    uint16_t gg[4];
+    load4<uint16_t>(p.goal, env0, p.B, gg);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g4[i] = gg[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g4[i] = p.fixed_goal;
+  }
+  uint8_t nd[4];
+  load4<uint8_t>(c.node, env0, p.B, nd);
+  int32_t ob[4];  // the obs of the state each env is in (what the previous step, or the reset, emitted)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
+      if (env0 + i < p.B) atomicOr(&p.ctl->err, GP_DERR_CTRL);
+      nd[i] = (uint8_t)(c.M - 1);
+    }
+    ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
+  }
+  float rsum = 0.f;
+  uint32_t eps = 0, lens = 0, nst = 0;
+  for (int k = 0; k < K; ++k) {
+    const size_t off = (size_t)k * p.B;
+    const uint64_t step = step0 + k;
+    int32_t a4[4];
+    uint8_t n4[4];
+    float r[4];
+    uint8_t tm[4], tr[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int env = env0 + i;
+      uint64_t k53 = 0;
+      uint32_t gi = 0, ai = 0, y = 0;
+      if (env < p.B) {
+        philox_draws(p, env, step, k53, gi, ai);
+        y = philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG, p.key0, p.key1).x[0] >> 1;
+      }
+      uint32_t o = (uint32_t)ob[i];
+      if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
+        if (env < p.B) atomicOr(&p.ctl->err, GP_DERR_CTRL);
+        o = (uint32_t)c.n_obs - 1u;
+      }
+      const uint32_t* row = cthr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
+      const uint32_t j = min(ctrl_search(row, c.L, y), (uint32_t)c.L - 1u);
+      const uint32_t a = (j * c.inv_m) >> 16;  // j / M
+      n4[i] = nd[i];
+      a4[i] = (int32_t)a;
+      counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], (int)a, k53, gi, ai, r[i], tm[i], tr[i], rsum, eps, lens);
+      nd[i] = (tm[i] | tr[i]) ? (uint8_t)0 : (uint8_t)(j - a * (uint32_t)c.M);  // j % M; episode end: node 0
+      ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
+      nst += env < p.B;
+    }
+    if (act) store4<int32_t>(act + off, env0, p.B, a4);
+    if (nodes) store4<uint8_t>(nodes + off, env0, p.B, n4);
+    if (rew) store4<float>(rew + off, env0, p.B, r);
+    if (term) store4<uint8_t>(term + off, env0, p.B, tm);
+    if (trunc) store4<uint8_t>(trunc + off, env0, p.B, tr);
+    if (obs) store4<int32_t>(obs + off, env0, p.B, ob);
+  }
+  store4<uint32_t>(p.ae, env0, p.B, ae4);
+  if (p.fixed_goal < 0) {
+    uint16_t gg[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) gg[i] = (uint16_t)g4[i];
+    store4<uint16_t>(p.goal, env0, p.B, gg);
+  }
+  store4<uint8_t>(c.node, env0, p.B, nd);
+  add_metrics(p, rsum, eps, lens, nst);
+}
+
 // Philox / replay reset: every env draws goal then agent from its own counter.
 template <int OK, bool REPLAY>
 __global__ __launch_bounds__(TPB) void grid_reset_counter(GridDev p, uint64_t step, void* __restrict__ obs) {
@@ -2772,6 +2906,10 @@ struct GridBackend : EnvBackend {
     else if (!strcmp(key, "autotune_steps")) *v = at_steps;
     else if (!strcmp(key, "autotune_wgrid_ns")) *v = (int64_t)(at_ms[0] * 1e6f);
     else if (!strcmp(key, "autotune_fused_ns")) *v = (int64_t)(at_ms[1] * 1e6f);
+    // philox mode: the counter's step index of the next reset / step (what a restatement of the draws needs)
+    else if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
     else return EnvBackend::query(key, v);
     return GP_OK;
   }
@@ -2808,6 +2946,14 @@ struct GridBackend : EnvBackend {
   }
   int metrics(double out[4]) override;
   int autotune(int K, int reps, int* chosen) override;
+  // closed-loop rollouts (grid_rollout_controller)
+  CtrlDev ctrl{};            // M == 0: no controller installed
+  DevBuf b_cthr, b_cnode;
+  int controller_unsupported(const char* what) const;
+  int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
+  int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
+                         hipStream_t s) override;
+  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override;
 #ifdef GP_STAMPS
   int debug_stamps(unsigned long long* out, int cap) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
@@ -3208,6 +3354,7 @@ static int dispatch_obs(int ok, F&& f) {
 
 int GridBackend::reset(void* obs, hipStream_t s) {
   GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * nslots, s));
+  if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
   const unsigned g1 = (unsigned)((B + TPB - 1) / TPB);
   const bool rgoal = d.fixed_goal < 0, ragent = d.fixed_agent < 0;
   const unsigned gp = (unsigned)grid_persist;
@@ -3426,6 +3573,119 @@ int GridBackend::rollout(int K, const void* act, void* obs, float* rew, uint8_t*
   if (e) return e;
   philox_step += (uint64_t)K;
   GP_HIP_CHECK(hipGetLastError());
+  return GP_OK;
+}
+
+// ---- closed-loop rollouts ----
+int GridBackend::controller_unsupported(const char* what) const {
+  if (rng_mode != GP_RNG_PHILOX) {
+    gp_set_error("%s: closed-loop rollouts need rng_mode philox", what);
+    return GP_E_UNSUPPORTED;
+  }
+  if (d.obs_kind != GP_OBS_HANSEN && d.obs_kind != GP_OBS_TABLE) {
+    gp_set_error("%s: the controller conditions on a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), not obs kind %d", what,
+                 d.obs_kind);
+    return GP_E_UNSUPPORTED;
+  }
+  return GP_OK;
+}
+
+int GridBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
+  if (int e = controller_unsupported("gp_set_controller")) return e;
+  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
+  if (!thr_host) {
+    ctrl = CtrlDev{};
+    int e;
+    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
+    return GP_OK;
+  }
+  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
+    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
+    return GP_E_INVALID;
+  }
+  const int L = d.nact * n_nodes;
+  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)L;
+  if (n > ((size_t)1 << 28)) {
+    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
+    return GP_E_INVALID;
+  }
+  constexpr uint32_t TOP = 1u << 31;
+  for (size_t r = 0; r < rows; ++r) {
+    const uint32_t* t = thr_host + r * L;
+    uint32_t prev = 0;
+    for (int i = 0; i < L; ++i) {
+      if (t[i] < prev || t[i] > TOP) {
+        gp_set_error("gp_set_controller: row (node %zu, obs %zu) is not nondecreasing within [0, 2^31] at entry %d",
+                     r / (size_t)n_obs, r % (size_t)n_obs, i);
+        return GP_E_INVALID;
+      }
+      prev = t[i];
+    }
+    if (prev != TOP) {
+      gp_set_error("gp_set_controller: row (node %zu, obs %zu) ends at %u, not 2^31", r / (size_t)n_obs,
+                   r % (size_t)n_obs, prev);
+      return GP_E_INVALID;
+    }
+  }
+  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
+  int e;
+  if ((e = b_cthr.alloc(n * sizeof(uint32_t))) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
+  GP_HIP_CHECK(hipMemcpy(b_cthr.p, thr_host, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  ctrl.thr = b_cthr.as<uint32_t>();
+  ctrl.node = b_cnode.as<uint8_t>();
+  ctrl.M = n_nodes;
+  ctrl.n_obs = n_obs;
+  ctrl.L = L;
+  ctrl.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
+  ctrl.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
+  // Staged in LDS behind the env's tables when both fit CTRL_LDS_BUDGET per block (measured faster at
+  // 6.5 and 26 KB tables); larger tables, and envs whose own tables are not in LDS, read the rows through the caches.
+  const int knob = gp_debug_knobs().ctrl_lds_max;
+  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
+  ctrl.lds_off = (d.lds.total > 0 && (size_t)d.lds.jt.off + n * sizeof(uint32_t) <= budget) ? d.lds.jt.off : -1;
+  return GP_OK;
+}
+
+int GridBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term,
+                                    uint8_t* trunc, hipStream_t s) {
+  if (int e = controller_unsupported("gp_rollout_controller")) return e;
+  if (!has_reset || !ctrl.M) {
+    gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
+                                                                      "(gp_set_controller)");
+    return GP_E_STATE;
+  }
+  int e = dispatch_obs(d.obs_kind, [&](auto okc) -> int {
+    constexpr int OK = decltype(okc)::value;
+    if constexpr (OK == GP_OBS_HANSEN || OK == GP_OBS_TABLE) {
+      timer.begin(s);
+      if (ctrl.lds_off >= 0)  // the controller table staged behind the env's tables (set_controller decided)
+        hipLaunchKernelGGL((grid_rollout_controller<OK, true, true>), dim3(d.nblk), dim3(TPB),
+                           (size_t)ctrl.lds_off + (size_t)ctrl.bytes, s, d, ctrl, K, philox_step, (int32_t*)obs, act,
+                           nodes, rew, term, trunc);
+      else if (d.lds.total > 0)  // the env's tables in LDS, as gp_rollout has them
+        hipLaunchKernelGGL((grid_rollout_controller<OK, true>), dim3(d.nblk), dim3(TPB), (size_t)d.lds.jt.off, s, d,
+                           ctrl, K, philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+      else
+        hipLaunchKernelGGL((grid_rollout_controller<OK, false>), dim3(d.nblk), dim3(TPB), 0, s, d, ctrl, K,
+                           philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+      timer.end(s);
+    }
+    return GP_OK;
+  });
+  if (e) return e;
+  philox_step += (uint64_t)K;
+  GP_HIP_CHECK(hipGetLastError());
+  return GP_OK;
+}
+
+int GridBackend::controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) {
+  if (int e = controller_unsupported("gp_controller_nodes")) return e;
+  if (!ctrl.M) {
+    gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
+    return GP_E_STATE;
+  }
+  if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
+  if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
   return GP_OK;
 }
 

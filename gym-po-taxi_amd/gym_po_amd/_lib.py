@@ -86,6 +86,9 @@ SIGNATURES = {
     "gp_plan_create": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     "gp_plan_run": (ctypes.c_int, [_vp]),
     "gp_plan_destroy": (None, [_vp]),
+    "gp_set_controller": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "gp_rollout_controller": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gp_controller_nodes": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "gp_get_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_replay": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -273,6 +273,119 @@ class NativeVecEnv:
             return keep.bufs
         return run, (out[0], out[1], out[2].view(torch.bool), out[3].view(torch.bool))
 
+    # ------------------------------------------------------------------ closed loop ----
+    _CTRL_OUTPUTS = ("obs", "actions", "nodes", "rew", "term", "trunc")
+
+    def _ctrl_fn(self, name):
+        fn = getattr(lib(), name, None)
+        if fn is None:  # an older library chosen through GYM_PO_AMD_LIB
+            raise _lib.GymPoError(f"{_lib.LIB_PATH} has no {name}: closed-loop rollouts need a current build")
+        return fn
+
+    def set_controller(self, probs=None, thresholds=None):
+        """Install the tabular controller of the closed-loop rollouts (FourRooms / ROOMS with a scalar obs in
+        rng_mode='philox'), or remove it when both arguments are None. `probs`: float [M, n_obs, A, M], the joint
+        probability of (action, next node) given (node, obs), or [n_obs, A] for a memoryless policy; lowered by
+        `controller.controller_thresholds`. `thresholds`: that uint32 [M, n_obs, A * M] table itself. n_obs is
+        `single_observation_space.n`, A the action count, M <= 8. Every env's node becomes 0. Raises GymPoError for
+        a table that does not fit the env or is not monotone up to 2^31, and for envs without closed-loop rollouts."""
+        fn = self._ctrl_fn("gp_set_controller")
+        if probs is not None and thresholds is not None:
+            raise ValueError("set_controller takes probs or thresholds, not both")
+        if probs is None and thresholds is None:
+            check(fn(self._handle, 0, 0, None), "gp_set_controller")
+            return
+        if probs is not None:
+            from .controller import controller_thresholds
+            thresholds = controller_thresholds(probs)
+        t = np.ascontiguousarray(thresholds)
+        if t.dtype != np.uint32 or t.ndim != 3:
+            raise ValueError(f"thresholds must be a uint32 array [M, n_obs, A * M], got {t.dtype} {t.shape}")
+        M, n_obs, L = t.shape
+        A = getattr(getattr(self, "single_action_space", None), "n", None)
+        if A is None or self._action_dtype != "int32":
+            raise _lib.GymPoError("set_controller: the env has no discrete action space")
+        if L != int(A) * M:
+            raise _lib.GymPoError(f"set_controller: rows of a {M}-node controller over {int(A)} actions have "
+                                  f"{int(A) * M} entries, got {L}")
+        n_space = getattr(getattr(self, "single_observation_space", None), "n", None)
+        if n_space is not None and n_obs != int(n_space):
+            raise _lib.GymPoError(f"set_controller: the table has n_obs = {n_obs}, the env's observation space "
+                                  f"{int(n_space)}")
+        check(fn(self._handle, M, n_obs, ctypes.c_void_p(t.ctypes.data)), "gp_set_controller")
+
+    def rollout_controller(self, K, out=None, store=_CTRL_OUTPUTS):
+        """K closed-loop steps in ONE launch: each env's action is drawn on the device by the installed controller
+        from the env's current observation and controller node (set_controller). Returns a dict of the outputs
+        named in `store`: obs [K, B] (the env's obs dtype), actions int32 [K, B] (the actions taken), nodes uint8
+        [K, B] (the node each action was chosen in), rew float32 [K, B], term / trunc bool [K, B]. Outputs left out
+        of `store` are not written at all (store=() is a pure policy evaluation, read through metrics()). `out`
+        may supply preallocated buffers as a dict by name (term / trunc as uint8), checked for shape, dtype, device
+        and contiguity (ValueError otherwise). Feeding `actions` to rollout() on a twin env of the same seed
+        reproduces obs, rew, term and trunc bit for bit."""
+        torch = _torch()
+        fn = self._ctrl_fn("gp_rollout_controller")
+        K = int(K)
+        if K < 0:
+            raise ValueError("K must be >= 0")
+        store = tuple(store)
+        for name in store:
+            if name not in self._CTRL_OUTPUTS:
+                raise ValueError(f"store: unknown output {name!r} (one of {self._CTRL_OUTPUTS})")
+        lead = (K, self.num_envs)
+        want = {"obs": ((K,) + self._obs_shape(), self._obs_dtype), "actions": (lead, torch.int32),
+                "nodes": (lead, torch.uint8), "rew": (lead, torch.float32), "term": (lead, torch.uint8),
+                "trunc": (lead, torch.uint8)}
+        if out is not None and not isinstance(out, dict):
+            raise ValueError("out must be a dict of tensors by output name")
+        bufs = {}
+        for name in store:
+            shape, dt = want[name]
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            elif not isinstance(t, torch.Tensor):
+                raise ValueError(f"out {name}: expected a torch tensor")
+            elif tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"out {name}: need a contiguous {dt} tensor of shape {shape} on {self.device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device} (contiguous={t.is_contiguous()})")
+            bufs[name] = t
+        ptr = lambda name: ctypes.c_void_p(bufs[name].data_ptr()) if name in bufs else None  # noqa: E731
+        check(fn(self._handle, K, ptr("obs"), ptr("actions"), ptr("nodes"), ptr("rew"), ptr("term"), ptr("trunc"),
+                 self._stream()), "gp_rollout_controller")
+        res = dict(bufs)
+        if "obs" in res:
+            res["obs"] = self._post_obs(res["obs"])
+        for name in ("term", "trunc"):
+            if name in res:
+                res[name] = res[name].view(torch.bool)
+        return res
+
+    @property
+    def controller_nodes(self):
+        """The controller node of every env, uint8 [B] on the device (a copy). Assigning an array-like [B] replaces
+        them (values below the controller's node count); reset() and set_controller() zero them."""
+        torch = _torch()
+        t = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
+        check(self._ctrl_fn("gp_controller_nodes")(self._handle, ctypes.c_void_p(t.data_ptr()), None, self._stream()),
+              "gp_controller_nodes")
+        return t
+
+    @controller_nodes.setter
+    def controller_nodes(self, nodes):
+        torch = _torch()
+        fn = self._ctrl_fn("gp_controller_nodes")
+        if not isinstance(nodes, torch.Tensor) or nodes.device.type == "cpu":
+            n = np.asarray(nodes.numpy() if isinstance(nodes, torch.Tensor) else nodes)
+            M = self.query("controller_nodes")
+            if n.size and M and (n.min() < 0 or n.max() >= M):
+                raise ValueError(f"controller_nodes: values must be in [0, {M})")
+            nodes = torch.as_tensor(n)
+        t = nodes.to(device=self.device, dtype=torch.uint8).contiguous()
+        if tuple(t.shape) != (self.num_envs,):
+            raise ValueError(f"controller_nodes: need {self.num_envs} values, got shape {tuple(t.shape)}")
+        check(fn(self._handle, None, ctypes.c_void_p(t.data_ptr()), self._stream()), "gp_controller_nodes")
+
     def autotune(self, K=20, reps=5):
         """Pick, on this device, the faster of the handle's interchangeable kernels for launches of K steps
         (numpy-mode FourRooms/ROOMS: the windowed and the fused kernel, bit-identical results) by timing `reps`

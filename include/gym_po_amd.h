@@ -203,6 +203,39 @@ int gp_plan_create(gp_env* env, int K, const void* actions, void* obs, float* re
 int gp_plan_run(gp_plan* plan);
 void gp_plan_destroy(gp_plan* plan);
 
+/* ---- closed-loop rollouts: a tabular finite-state controller evaluated inside the rollout kernel ----
+ * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE); every other kind, rng mode and obs kind:
+ * GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host, one step() per action.)
+ *
+ * The controller has M = n_nodes nodes (1..8; M = 1 is a memoryless policy obs -> action distribution). With A the
+ * env's action count and L = A * M, thr_host is uint32 [M][n_obs][L] (host memory): row (node, obs) holds the
+ * cumulative probabilities of the joint choice j = action * M + next_node, scaled to 2^31. Each row must be
+ * nondecreasing, hold no entry above 2^31 and end at 2^31 (else GP_E_INVALID). n_obs is the size of the env's scalar
+ * observation space; an obs >= n_obs met on the device is clamped and flagged (gp_check: GP_E_DEVICE).
+ *
+ * Per env-step, before the env transition: obs = the env's scalar obs of the state it is in (the reset obs, then the
+ * post-autoreset obs of the previous step; computed from the state, never read from an output buffer); one
+ * Philox4x32-10 block with counter (env, step_lo, step_hi, 0x67706f63) under the env draws' key, step being the same
+ * host-tracked index the env's own draws of that step use (theirs carry 0x67706f21); y = x0 >> 1;
+ * j = #{i < L : y >= thr[node][obs][i]}; action = j / M; after the transition node = j % M, or 0 if the step ended
+ * the episode (terminated | truncated). The env's draws and the step index advance exactly as in gp_rollout: feeding
+ * the emitted actions to gp_rollout on a twin handle reproduces every output and the final state bit for bit.
+ *
+ * gp_set_controller validates the table, uploads it synchronously and zeroes every node; thr_host = NULL removes the
+ * controller. The nodes (uint8 [B], handle state) persist across calls; gp_reset zeroes them; gp_step / gp_rollout
+ * leave them alone.
+ * gp_rollout_controller runs K steps in one launch. obs [K,B] int32, rew [K,B] float, term / trunc [K,B] uint8 as
+ * gp_rollout; actions int32 [K,B]: the actions taken; nodes uint8 [K,B]: the node each action was chosen in. Every
+ * output pointer may be NULL (not stored); with all of them NULL the call is a pure policy evaluation, read through
+ * gp_metrics. GP_E_STATE before gp_reset or without a controller.
+ * gp_controller_nodes: get (device uint8 [B], may be NULL) receives the nodes, then set (device uint8 [B], may be
+ * NULL) replaces them, both asynchronously on `stream`. A node >= n_nodes is clamped and flagged by the next
+ * closed-loop launch. */
+int gp_set_controller(gp_env* env, int n_nodes, int n_obs, const uint32_t* thr_host);
+int gp_rollout_controller(gp_env* env, int K, void* obs, int32_t* actions, uint8_t* nodes, float* rew, uint8_t* term,
+                          uint8_t* trunc, void* stream);
+int gp_controller_nodes(gp_env* env, uint8_t* get, const uint8_t* set, void* stream);
+
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. CARFLAG: s f32[B,3]
@@ -231,7 +264,8 @@ int gp_metrics(gp_env* env, double out[4]);
 /* Syncs the handle's device and returns GP_E_DEVICE if any launch since the last seed failed on the
  * device (numpy-mode GRID: a persistent kernel's cross-block wait timed out; any kind: an action outside
  * [-n, n) was given, where the reference raises IndexError at msrooms.py:400 / rooms.py:208 /
- * extended_taxi.py:248 — the device clamps it and flags the handle), else GP_OK. The
+ * extended_taxi.py:248 — the device clamps it and flags the handle; closed-loop rollouts: an obs or node outside the
+ * controller table, clamped and flagged likewise), else GP_OK. The
  * asynchronous step/rollout calls cannot report such failures themselves; gp_metrics and
  * gp_get_rng_state run the same check. (No reference counterpart: numpy steps are synchronous.) */
 int gp_check(gp_env* env);
@@ -245,7 +279,9 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
 /* Introspection of a handle (host-only, no sync): key = "num_envs", "rng_mode", and for GRID
  * "fused_blocks" (persistent grid size of the fused numpy rollout, 0 = not eligible),
  * "fused_tiles_per_block", "fused_staged" (1 = LDS-staged outputs + store waves),
- * "fused_tile_envs". Unknown keys return GP_E_INVALID. */
+ * "fused_tile_envs", "philox_step" (GP_RNG_PHILOX: the counter's step index that the next reset / step draws
+ * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
+ * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS). Unknown keys return GP_E_INVALID. */
 int gp_query(const gp_env* env, const char* key, int64_t* value);
 /* ---- the normal sampler of rng_mode=philox (C-ROOMS noise), diagnostics ----
  * Replaces numpy's Generator.standard_normal (numpy/random/src/distributions/distributions.c,
@@ -294,7 +330,10 @@ int gp_profile_read_resolver(gp_env* env, double* total_ms, int64_t* n_launches)
  *   generic philox rollout even where a compile-time-specialised one exists), "no_wgrid" (GRID numpy mode: 1 =
  *   never the windowed kernel csrc/wgrid.hip), "wg_halo" (its window halo: 256 or 512 draws), "wg_bias" (added
  *   to its predicted reset count: forces window regenerations), "wg_tmode" (its timing-study variants, TM_* in
- *   csrc/wgrid.hip; results invalid for some). gp_debug_reset restores the defaults. Unknown key: GP_E_INVALID. */
+ *   csrc/wgrid.hip; results invalid for some), "ctrl_lds_max" (GRID closed-loop rollouts, read by
+ *   gp_set_controller instead: the controller table is staged in LDS when the env's tables plus the table take at
+ *   most this many bytes of LDS per block; 0 = always read from global memory, -1 = the default, 32 KB).
+ *   gp_debug_reset restores the defaults. Unknown key: GP_E_INVALID. */
 int gp_debug_set(const char* key, int64_t value);
 void gp_debug_reset(void);
 
