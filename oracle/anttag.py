@@ -30,6 +30,13 @@ class AntTagOracle:
         cy, cx = np.divmod(np.arange(nc), size)
         d2 = (cy[:, None] - cy[None, :]) ** 2 + (cx[:, None] - cx[None, :]) ** 2
         self.valid_targets = [np.flatnonzero(d2[a] > min_start_dist2) for a in range(nc)]
+        self._cnt = np.array([len(v) for v in self.valid_targets], dtype=np.int64)
+        if (self._cnt == 0).any():  # the device refuses such a config too (GP_E_INVALID)
+            raise ValueError(f"anttag: no target cell farther than sqrt({min_start_dist2}) from cell "
+                             f"{int(np.flatnonzero(self._cnt == 0)[0])}")
+        self._lists = np.zeros((nc, nc), np.int64)  # row a: valid_targets[a], zero padded
+        for a, v in enumerate(self.valid_targets):
+            self._lists[a, :len(v)] = v
         self.ant = np.zeros(num_envs, np.int64)
         self.target = np.zeros(num_envs, np.int64)
         self.elapsed = np.zeros(num_envs, np.int64)
@@ -39,15 +46,14 @@ class AntTagOracle:
         x0, x1, x2, _ = env_step_words(self.B, step, TAG, key)
         choose = (x0 >> np.uint32(30)).astype(np.int64)
         ant = lemire_value(x1, self.N * self.N)
-        cnt = np.array([len(v) for v in self.valid_targets])[ant]
+        cnt = self._cnt[ant]
         k = ((x2.astype(np.uint64) * cnt.astype(np.uint64)) >> np.uint64(32)).astype(np.int64)  # Lemire, n = cnt
         return dict(choose=choose, ant=ant, tgt=k)
 
     def _reset(self, mask, dr):
         ant = dr["ant"][mask]
         k = dr["tgt"][mask]
-        tgt = np.array([self.valid_targets[a][min(kk, len(self.valid_targets[a]) - 1)] for a, kk in zip(ant, k)],
-                       dtype=np.int64)
+        tgt = self._lists[ant, np.minimum(k, self._cnt[ant] - 1)]  # an index past the list takes its last cell
         self.ant[mask] = ant
         self.target[mask] = tgt
         self.elapsed[mask] = 0

@@ -11,6 +11,7 @@ Here:
 - out-of-range actions given as host arrays raise the reference's IndexError before anything is launched;
   given as device tensors they cannot be checked without a sync, so the kernels flag the handle
   (GP_DERR_ACTION) and check() / metrics() raise GymPoError; reseeding clears the flag.
+The grid Ant-Tag kernel (5 actions, philox) has its own wrap and flag code and is held to the same three rules.
 """
 import numpy as np
 import pytest
@@ -69,10 +70,39 @@ def test_negative_actions_rooms_ordinal_fused(gpu_device):
     _rollouts_vs_oracle(env, ora, 8, (16,), seed=44)
 
 
-@pytest.mark.parametrize("kind", ["fourrooms", "rooms"])
+def _anttag_negative_actions_vs_oracle(gpu_device):
+    from gym_po_amd import AntTagGridEnv
+    from oracle.anttag import AntTagOracle
+    from oracle.philox import philox_key
+    B, T, seed = 4099, 30, 47
+    env, ora = AntTagGridEnv(B, time_limit=12, device=gpu_device), AntTagOracle(B, time_limit=12)
+    key = philox_key(seed)
+    np.testing.assert_array_equal(env.reset(seed=seed)[0].cpu().numpy(), ora.reset(ora.philox_draws(0, key)))
+    rng = np.random.default_rng(48)
+    for t in range(T):
+        a = rng.integers(-5, 5, B)
+        o, r, d, tr, _ = env.step(a if t % 2 else torch_i32(a, gpu_device))  # host arrays and device tensors
+        oo, ro, do, tro = ora.step(a, ora.philox_draws(t + 1, key))
+        np.testing.assert_array_equal(o.cpu().numpy(), oo, err_msg=f"t={t}")
+        np.testing.assert_array_equal(r.cpu().numpy(), ro)
+        np.testing.assert_array_equal(d.cpu().numpy(), do)
+        np.testing.assert_array_equal(tr.cpu().numpy(), tro)
+    env.check()  # in-range negative actions are not flagged
+    for x, y in zip(env.get_state(), (ora.ant, ora.target, ora.elapsed)):
+        np.testing.assert_array_equal(x.cpu().numpy(), y)
+
+
+def torch_i32(a, device):
+    import torch
+    return torch.as_tensor(a.astype(np.int32), device=device)
+
+
+@pytest.mark.parametrize("kind", ["fourrooms", "rooms", "anttag"])
 def test_negative_actions_two_kernel_path(kind, gpu_device):
     from gym_po_amd import MultistoryFourRoomsEnv, RoomsEnv
     from gym_po_amd._lib import debug_knobs
+    if kind == "anttag":  # one kernel only: the philox rollout, against its own oracle
+        return _anttag_negative_actions_vs_oracle(gpu_device)
     B, T = (1 << 16) + 5, 30
     with debug_knobs(disable_fused=1):
         if kind == "fourrooms":
@@ -97,7 +127,9 @@ def test_negative_actions_two_kernel_path(kind, gpu_device):
 
 
 def _make(kind, gpu_device, **kw):
-    from gym_po_amd import HansenTaxiVecEnv, MultistoryFourRoomsEnv, RoomsEnv
+    from gym_po_amd import AntTagGridEnv, HansenTaxiVecEnv, MultistoryFourRoomsEnv, RoomsEnv
+    if kind == "anttag":
+        return AntTagGridEnv(4096, device=gpu_device, **kw), 5
     if kind == "fourrooms":
         return MultistoryFourRoomsEnv(4096, grid_z=1, obs_type="hansen", device=gpu_device, **kw), 4
     if kind == "rooms":
@@ -106,7 +138,8 @@ def _make(kind, gpu_device, **kw):
 
 
 @pytest.mark.parametrize("kind,mode,fused", [("fourrooms", "numpy", True), ("fourrooms", "numpy", False),
-                                             ("rooms", "philox", True), ("taxi", "philox", True)])
+                                             ("rooms", "philox", True), ("taxi", "philox", True),
+                                             ("anttag", "philox", True)])
 @pytest.mark.parametrize("bad", ["n", "-n-1"])
 def test_out_of_range_device_actions_flag_the_handle(kind, mode, fused, bad, gpu_device):
     import torch
@@ -127,7 +160,7 @@ def test_out_of_range_device_actions_flag_the_handle(kind, mode, fused, bad, gpu
     env.check()
 
 
-@pytest.mark.parametrize("kind", ["fourrooms", "rooms", "taxi"])
+@pytest.mark.parametrize("kind", ["fourrooms", "rooms", "taxi", "anttag"])
 def test_out_of_range_host_actions_raise_index_error(kind, gpu_device):
     env, n = _make(kind, gpu_device)
     env.reset(seed=1)
