@@ -301,6 +301,9 @@ int gp_create(int kind, const void* config, int64_t num_envs, int device, int rn
     case GP_KIND_CARFLAG:
       be = make_carflag_backend((const gp_carflag_config*)config, num_envs, device, rng_mode, &err);
       break;
+    case GP_KIND_ROCKSAMPLE:
+      be = make_rocksample_backend((const gp_rocksample_config*)config, num_envs, device, rng_mode, &err);
+      break;
     default: gp_set_error("gp_create: unknown kind %d", kind); return GP_E_INVALID;
   }
   if (!be) return err ? err : GP_E_INVALID;

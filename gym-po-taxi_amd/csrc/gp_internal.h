@@ -44,7 +44,7 @@ struct GpDebugKnobs {
   int wg_fill_simd = 0;     // GRID windowed kernel: per-SIMD window-row deltas, 4 signed nibbles (0 = WG_FILL_SIMD)
   int64_t wg_fill_wave = 0; // GRID windowed kernel: per-wave deltas on top, 8 signed nibbles (wave 0 lowest)
   int ctrl_lds_max = -1;    // GRID closed-loop rollouts: dynamic LDS bytes per block up to which the controller table is staged in LDS (0 = never; -1 = grid.hip CTRL_LDS_BUDGET); read by gp_set_controller
-  int persist_bpc = 0;      // TAXI / CROOMS / ANT-TAG streaming rollouts: blocks per CU (0 = every resident block, persistent_grid)
+  int persist_bpc = 0;      // TAXI / CROOMS / ANT-TAG / ROCKSAMPLE streaming rollouts: blocks per CU (0 = every resident block, persistent_grid)
 };
 const GpDebugKnobs& gp_debug_knobs();
 
@@ -101,7 +101,8 @@ struct EnvBackend {
     gp_set_error("replay mode not supported by this env kind");
     return GP_E_UNSUPPORTED;
   }
-  // Closed-loop rollouts (gp_set_controller / gp_rollout_controller / gp_controller_nodes): GRID in philox mode.
+  // Closed-loop rollouts (gp_set_controller / gp_rollout_controller / gp_controller_nodes): GRID in philox mode,
+  // ROCKSAMPLE.
   virtual int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
     gp_set_error("controllers are not supported by this env kind");
     return GP_E_UNSUPPORTED;
@@ -159,6 +160,8 @@ std::unique_ptr<EnvBackend> make_anttag_backend(const gp_anttag_config* cfg, int
                                                 int* err);
 std::unique_ptr<EnvBackend> make_carflag_backend(const gp_carflag_config* cfg, int64_t B, int device, int rng_mode,
                                                  int* err);
+std::unique_ptr<EnvBackend> make_rocksample_backend(const gp_rocksample_config* cfg, int64_t B, int device,
+                                                    int rng_mode, int* err);
 
 // Small device-buffer owner.
 struct DevBuf {

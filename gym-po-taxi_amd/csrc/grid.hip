@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "gp_ctrl.h"
 #include "gp_internal.h"
 #include "grid_shared.h"
 
@@ -2673,42 +2674,10 @@ __global__ __launch_bounds__(TPB) void grid_rollout_counter(GridDev p, int K, ui
 // state in registers. The row is read from global memory (L1/L2: ROOMS Hansen-8 tables are 74 KB-4.7 MB, FourRooms
 // Hansen-8 1.9 MB and up), or, CL, from a copy of the table staged in LDS behind the env's tables when both are small
 // (FourRooms Hansen-4: 6.5 KB with M = 1, 26 KB with M = 2). Rows are 16-B aligned: L = nact * M is a multiple of 4.
-constexpr uint32_t CTRL_TAG = 0x67706f63u;  // the env draws carry 0x67706f21 (philox_draws)
-struct CtrlDev {
-  const uint32_t* thr;  // [M][n_obs][L]: nondecreasing rows, entries <= 2^31, last == 2^31 (validated on upload)
-  uint8_t* node;        // [B] the controller node of each env
-  int32_t M, n_obs, L;
-  uint32_t inv_m;       // ceil(2^16 / M): j / M == (j * inv_m) >> 16 for j < 64, M <= 8
-  int32_t lds_off, bytes;  // lds_off >= 0: the table is staged at this offset of the dynamic LDS (CL launches); its size
-};
+// CTRL_TAG, CtrlDev and the row search ctrl_search: gp_ctrl.h (shared with rocksample.hip).
 // Largest dynamic LDS per block (env tables + controller table) with the controller staged: 5 blocks per CU stay
 // resident, more than the 4 a 2^20-env launch puts there.
 constexpr int CTRL_LDS_BUDGET = 32 * 1024;
-
-__device__ __forceinline__ uint32_t ctrl_count4(const uint4 q, uint32_t y) {
-  return (uint32_t)(y >= q.x) + (uint32_t)(y >= q.y) + (uint32_t)(y >= q.z) + (uint32_t)(y >= q.w);
-}
-// #{i < L : y >= row[i]} for a nondecreasing row whose last entry exceeds y (y < 2^31). Up to 16 entries: every
-// 16-B quad is loaded (independent loads, one latency) and counted. Longer rows: a branch-free binary search over
-// the quads' last entries for the first quad not entirely <= y (never past the last quad), then that quad's count.
-__device__ __forceinline__ uint32_t ctrl_search(const uint32_t* __restrict__ row, int L, uint32_t y) {
-  const uint4* q4 = reinterpret_cast<const uint4*>(row);
-  const int nq = L >> 2;
-  if (nq <= 4) {
-    uint32_t j = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (q < nq) j += ctrl_count4(q4[q], y);
-    return j;
-  }
-  int base = 0, len = nq;  // the number of full quads lies in [base, base + len - 1]
-  while (len > 1) {
-    const int half = len >> 1;
-    base = (y >= row[4 * (base + half - 1) + 3]) ? base + half : base;
-    len -= half;
-  }
-  return 4u * (uint32_t)base + ctrl_count4(q4[base], y);
-}
 
 template <int OK, bool LT = false, bool CL = false>
 __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDev c, int K, uint64_t step0,
@@ -3609,24 +3578,7 @@ int GridBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host
     gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
     return GP_E_INVALID;
   }
-  constexpr uint32_t TOP = 1u << 31;
-  for (size_t r = 0; r < rows; ++r) {
-    const uint32_t* t = thr_host + r * L;
-    uint32_t prev = 0;
-    for (int i = 0; i < L; ++i) {
-      if (t[i] < prev || t[i] > TOP) {
-        gp_set_error("gp_set_controller: row (node %zu, obs %zu) is not nondecreasing within [0, 2^31] at entry %d",
-                     r / (size_t)n_obs, r % (size_t)n_obs, i);
-        return GP_E_INVALID;
-      }
-      prev = t[i];
-    }
-    if (prev != TOP) {
-      gp_set_error("gp_set_controller: row (node %zu, obs %zu) ends at %u, not 2^31", r / (size_t)n_obs,
-                   r % (size_t)n_obs, prev);
-      return GP_E_INVALID;
-    }
-  }
+  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L)) return e;
   ctrl = CtrlDev{};  // (no controller if an allocation below fails)
   int e;
   if ((e = b_cthr.alloc(n * sizeof(uint32_t))) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed

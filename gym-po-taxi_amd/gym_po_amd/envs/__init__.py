@@ -4,7 +4,8 @@ from .extended_taxi import (EXTENDED_TAXI_MAP, TAXI_MAP, ExtendedHansenTaxiVecEn
                             HansenTaxiVecEnv, TaxiVecEnv)
 from .ant_tag_grid import AntTagGridEnv
 from .car_flag import CarVecEnv, DiscreteActionCarVecEnv
+from .rocksample import RockSample, rocksample_sensor_thresholds
 
 __all__ = ["RoomsEnv", "CRoomsEnv", "MultistoryFourRoomsEnv", "TaxiVecEnv", "HansenTaxiVecEnv",
            "ExtendedTaxiVecEnv", "ExtendedHansenTaxiVecEnv", "TAXI_MAP", "EXTENDED_TAXI_MAP", "AntTagGridEnv",
-           "CarVecEnv", "DiscreteActionCarVecEnv"]
+           "CarVecEnv", "DiscreteActionCarVecEnv", "RockSample", "rocksample_sensor_thresholds"]

@@ -18,6 +18,8 @@
  *                                                                gym_po/envs/ant_tag.py:88-157
  *   gp_create(GP_KIND_CARFLAG) CarVecEnv.__init__ / DiscreteActionCarVecEnv.__init__
  *                                                                gym_po/envs/car_flag.py:50-85, :289-299
+ *   gp_create(GP_KIND_ROCKSAMPLE) RockSample (the reference has only the Obs / ACTION enums and a constructor
+ *                             signature; the rules are build-defined) gym_po/envs/rocksample/rocksample.py
  *   gp_seed / gp_seed_words   gymnasium Env.reset(seed=) -> seeding.np_random(seed)
  *                             (msrooms.py:376, rooms.py:184, extended_taxi.py:239, crooms.py:246-249)
  *   gp_reset                  *.reset()      msrooms.py:369-381, rooms.py:177-189,
@@ -57,6 +59,7 @@ extern "C" {
 #define GP_KIND_CROOMS 3
 #define GP_KIND_ANTTAG 4
 #define GP_KIND_CARFLAG 5 /* Car-Flag: 1-D heaven/hell POMDP (car_flag.py) */
+#define GP_KIND_ROCKSAMPLE 6 /* RockSample (Smith & Simmons 2004), build-defined rules: gp_rocksample_config */
 
 /* ---- RNG modes ---- */
 #define GP_RNG_NUMPY 0   /* seed-identical to numpy Generator(PCG64(SeedSequence(seed))): GRID, CROOMS, TAXI, CARFLAG */
@@ -158,6 +161,40 @@ typedef struct gp_carflag_config {
   const double* action_table; /* [n] forces of the discrete actions (np.linspace(-1, 1, n)); else NULL */
 } gp_carflag_config;
 
+/* RockSample (GP_KIND_ROCKSAMPLE; GP_RNG_PHILOX only: there is no reference stream, so GP_RNG_NUMPY / GP_RNG_REPLAY
+ * return GP_E_UNSUPPORTED). The reference names the env and never builds it; these rules are this build's.
+ *   grid     height x width cells, 1 <= height, width <= 16, cell = y * width + x, north is y - 1.
+ *   rocks    n_rocks (1..16) distinct cells; per env a good mask, bit i set = rock i is good.
+ *   actions  A = 5 + n_rocks: 0 N, 1 E, 2 S, 3 W, 4 SAMPLE, 5 + i = CHECK rock i. [-A, 0) wraps as numpy indexing
+ *            does; anything else is flagged GP_DERR_ACTION and clamped.
+ *   step     elapsed += 1, reading = NULL (0). N / S / W: move if the target is inside the grid (step_reward), else
+ *            stay (wall_reward). E: the same, except that from the last column the agent exits: terminated,
+ *            exit_reward. SAMPLE on rock i's cell: good_reward if bit i is set, else bad_reward; bit i is cleared.
+ *            SAMPLE elsewhere: empty_reward. CHECK i: check_reward; with y = x0 >> 1,
+ *            correct = y < sensor_thr[cell][i], the reading is GOOD (1) if (bit i) == correct, else BAD (2).
+ *   end      truncated = elapsed >= time_limit (gymnasium TimeLimit), independent of terminated. On either the env
+ *            resets in the same step: agent on init_cell, mask = x1 & (2^n_rocks - 1), elapsed = 0; the step's obs
+ *            is that of the reset state with reading NULL.
+ *   draws    one Philox4x32-10 block per (env, step), counter (env, step_lo, step_hi, 0x726f636b) under the handle's
+ *            key, step being the host-tracked index of the other philox kinds: x0 the check, x1 the reset mask.
+ *            gp_reset draws every mask from x1 of the block at the reset's step index.
+ *   obs      int32 [B]: the reading (obs_cell = 0, 3 values) or cell * 3 + reading (obs_cell = 1).
+ *   state    gp_get_state / gp_set_state: agent cell, good mask, elapsed, int32 [B] each (set clamps the cell to the
+ *            grid and elapsed to [0, 65535], keeps the low n_rocks bits of the mask, and makes the last reading NULL).
+ * GP_E_INVALID: a side or n_rocks out of range, duplicate rocks, a rock or init_cell off the grid, time_limit outside
+ * [1, 65535] (elapsed is kept in 16 bits), a sensor_thr entry above 2^31. */
+typedef struct gp_rocksample_config {
+  int32_t height, width, n_rocks;
+  const int32_t* rocks;       /* [n_rocks] rock cells                                                */
+  int32_t init_cell;          /* the agent's cell at every episode start                            */
+  const uint32_t* sensor_thr; /* [height*width][n_rocks]: P(check of rock i from cell is right) * 2^31, <= 2^31
+                                 (lowered by the caller, e.g. floor(0.5 * (1 + 2^(-d / d0)) * 2^31): no libm
+                                 call of the library decides a result)                                */
+  int32_t obs_cell;           /* 0: obs = reading; 1: obs = cell * 3 + reading                       */
+  int32_t time_limit;
+  float exit_reward, good_reward, bad_reward, empty_reward, check_reward, step_reward, wall_reward;
+} gp_rocksample_config;
+
 typedef struct gp_env gp_env;
 
 const char* gp_last_error(void);
@@ -204,8 +241,9 @@ int gp_plan_run(gp_plan* plan);
 void gp_plan_destroy(gp_plan* plan);
 
 /* ---- closed-loop rollouts: a tabular finite-state controller evaluated inside the rollout kernel ----
- * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE); every other kind, rng mode and obs kind:
- * GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host, one step() per action.)
+ * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), and ROCKSAMPLE (either obs); every other
+ * kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
+ * one step() per action.)
  *
  * The controller has M = n_nodes nodes (1..8; M = 1 is a memoryless policy obs -> action distribution). With A the
  * env's action count and L = A * M, thr_host is uint32 [M][n_obs][L] (host memory): row (node, obs) holds the
@@ -220,6 +258,11 @@ void gp_plan_destroy(gp_plan* plan);
  * j = #{i < L : y >= thr[node][obs][i]}; action = j / M; after the transition node = j % M, or 0 if the step ended
  * the episode (terminated | truncated). The env's draws and the step index advance exactly as in gp_rollout: feeding
  * the emitted actions to gp_rollout on a twin handle reproduces every output and the final state bit for bit.
+ * ROCKSAMPLE: the obs includes the reading of the previous step, which the handle keeps beside its state (every
+ * step, open or closed loop, records it; gp_reset and gp_set_state make it NULL); the env draws carry 0x726f636b.
+ * A = 5 + n_rocks need not be a multiple of 4: thr_host rows hold exactly L = A * M entries, and the library pads each
+ * uploaded row to a multiple of 4 entries with 2^31, which no y reaches. A * M > 64 is GP_E_INVALID (the j / M
+ * multiply is exact below 64).
  *
  * gp_set_controller validates the table, uploads it synchronously and zeroes every node; thr_host = NULL removes the
  * controller. The nodes (uint8 [B], handle state) persist across calls; gp_reset zeroes them; gp_step / gp_rollout
@@ -238,7 +281,8 @@ int gp_controller_nodes(gp_env* env, uint8_t* get, const uint8_t* set, void* str
 
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
- * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. CARFLAG: s f32[B,3]
+ * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
+ * mask, elapsed. CARFLAG: s f32[B,3]
  * (position, velocity, direction), elapsed i32[B], heavens f32[B] (+-1), priests f32[B] (+-0.5; set takes
  * both by sign). */
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream);
@@ -281,7 +325,8 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * "fused_tiles_per_block", "fused_staged" (1 = LDS-staged outputs + store waves),
  * "fused_tile_envs", "philox_step" (GP_RNG_PHILOX: the counter's step index that the next reset / step draws
  * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
- * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS). Unknown keys return GP_E_INVALID. */
+ * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE: always 0). Unknown keys return
+ * GP_E_INVALID. */
 int gp_query(const gp_env* env, const char* key, int64_t* value);
 /* ---- the normal sampler of rng_mode=philox (C-ROOMS noise), diagnostics ----
  * Replaces numpy's Generator.standard_normal (numpy/random/src/distributions/distributions.c,
