@@ -11,7 +11,10 @@
 //           |vy| == |vx| (none when v = 0). A step leaving the cage is not taken (:120-121).
 //   tag     d^2 <= tag_radius2 (1.5 m -> 2): reward tag_reward, terminated (:147-150)
 //   obs     int32 [ant y, ant x, target y, target x], the target replaced by (-1, -1) unless
-//           d^2 < visible_radius2 (3 m -> 9) (:77-86, :153)
+//           d^2 < visible_radius2 (3 m -> 9) (:77-86, :153); or, with obs_index = 1, the scalar int32
+//           ant cell * (nc + 1) + (visible ? target cell : nc), nc = size^2: the same information as the vector
+//           (a bijection onto the values it takes), in Discrete(nc * (nc + 1)), for tabular agents and the
+//           closed-loop rollouts (gp_set_controller: index obs, philox mode; A = 5, M <= 8)
 //   reset   ant uniform over the cells; target uniform over the cells with d^2 > min_start_dist2
 //           (5 m -> 25): the law of the rejection loop of reset_model (:88-103)
 //   trunc   elapsed >= time_limit (gymnasium TimeLimit, max_episode_steps=500, envs/__init__.py:15-19)
@@ -21,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "gp_ctrl.h"
 #include "gp_internal.h"
 
 namespace {
@@ -278,6 +282,161 @@ __global__ __launch_bounds__(TPB) void anttag_reset(AtDev p, uint64_t step, int4
   }
 }
 
+// ------------------------------------------------------------------ index obs (obs_index = 1) ----
+// The scalar obs of a state word: ant * (nc + 1) + (visible ? target : nc).
+__device__ __forceinline__ int32_t at_obs_idx(const AtDev& p, uint32_t u) {
+  const int N = p.N, ant = (int)(u & 0xFFu), tgt = (int)((u >> 8) & 0xFFu);
+  const int ay = cdiv(p, ant), ax = ant - ay * N, ty = cdiv(p, tgt), tx = tgt - ty * N;
+  const int dy = ay - ty, dx = ax - tx;
+  return ant * (p.ncells + 1) + (dy * dy + dx * dx < p.vis_r2 ? tgt : p.ncells);
+}
+
+// A thread's 4 consecutive envs as one access (16 B of 4-byte elements, 4 B of flags) when quad_ok, else element by
+// element (the ragged tail, caller buffers off their boundary): chosen per buffer and per step, as in rocksample.hip.
+template <class T>
+__device__ __forceinline__ void load4(const T* b, int env0, int B, T (&v)[EPT]) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
+  if (quad_ok(b, env0, B, sizeof(T))) {
+    if constexpr (sizeof(T) == 4) {
+      const uint4 q = *reinterpret_cast<const uint4*>(b + env0);
+      const uint32_t w[EPT] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) v[i] = __builtin_bit_cast(T, w[i]);
+    } else {
+      const uint32_t q = *reinterpret_cast<const uint32_t*>(b + env0);
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) v[i] = (T)((q >> (8 * i)) & 0xFFu);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) v[i] = env0 + i < B ? b[env0 + i] : T(0);
+  }
+}
+template <class T>
+__device__ __forceinline__ void store4(T* b, int env0, int B, const T (&v)[EPT]) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
+  if (quad_ok(b, env0, B, sizeof(T))) {
+    if constexpr (sizeof(T) == 4) {
+      *reinterpret_cast<uint4*>(b + env0) =
+          make_uint4(__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
+                     __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3]));
+    } else {
+      *reinterpret_cast<uint32_t*>(b + env0) =
+          (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < EPT; ++i)
+      if (env0 + i < B) b[env0 + i] = v[i];
+  }
+}
+
+// K steps of every env with the index obs: the geometry of anttag_rollout (persistent grid-stride loop over 1,024-env
+// tiles, 4 consecutive envs per thread, the state word in registers across the K steps), without its obs transpose
+// through LDS: a thread's 4 scalar obs are one 16-B store. CTRL = false: the actions come from `act` [K, B], loaded
+// one step ahead. CTRL = true (gp_rollout_controller, philox): each action is drawn by the installed controller from
+// the obs of the state word and the env's node (gp_ctrl.h; the rows are read from global memory); `aout` / `nodes`
+// receive the actions and nodes. Every output pointer may be null (not stored): gp_rollout passes all four of its own.
+template <bool REPLAY, bool CTRL>
+__global__ __launch_bounds__(TPB) void anttag_rollout_idx(AtDev p, CtrlDev c, int K, uint64_t step0,
+                                                          const int32_t* __restrict__ act, int32_t* __restrict__ obs,
+                                                          int32_t* __restrict__ aout, uint8_t* __restrict__ nodes,
+                                                          float* __restrict__ rew, uint8_t* __restrict__ term,
+                                                          uint8_t* __restrict__ trunc) {
+  static_assert(!(REPLAY && CTRL), "closed-loop rollouts draw from the philox stream");
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  stage_tables(p, lds);
+  __syncthreads();
+  float rsum = 0.f;
+  uint32_t eps = 0, lens = 0, nst = 0;
+  for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
+    const int env0 = tile * EPB + threadIdx.x * EPT;
+    uint32_t u[EPT];
+    load4<uint32_t>(p.st, env0, p.B, u);
+    uint8_t nd[EPT] = {0, 0, 0, 0};
+    int32_t a_nxt[EPT] = {0, 0, 0, 0};
+    if constexpr (CTRL) {
+      load4<uint8_t>(c.node, env0, p.B, nd);
+#pragma unroll
+      for (int i = 0; i < EPT; ++i)
+        if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
+          if (env0 + i < p.B) atomicOr(p.derr, GP_DERR_CTRL);
+          nd[i] = (uint8_t)(c.M - 1);
+        }
+    } else {
+      if (K > 0) load4<int32_t>(act, env0, p.B, a_nxt);
+    }
+    for (int k = 0; k < K; ++k) {
+      const size_t off = (size_t)k * p.B;
+      const uint64_t step = step0 + (uint64_t)k;
+      int32_t a[EPT];
+      uint32_t jj[EPT] = {0, 0, 0, 0};
+      uint8_t n4[EPT];
+      if constexpr (CTRL) {
+        const uint32_t lreal = (uint32_t)(NACT * c.M);  // entries of a row before its padding to 16-B quads
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) {
+          const int env = env0 + i;
+          const uint32_t y = env < p.B ? philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG,
+                                                       p.key0, p.key1).x[0] >> 1
+                                       : 0u;
+          uint32_t o = (uint32_t)at_obs_idx(p, u[i]);
+          if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
+            if (env < p.B) atomicOr(p.derr, GP_DERR_CTRL);
+            o = (uint32_t)c.n_obs - 1u;
+          }
+          const uint32_t* row = c.thr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
+          jj[i] = min(ctrl_search(row, c.L, y), lreal - 1u);
+          a[i] = (int32_t)((jj[i] * c.inv_m) >> 16);  // j / M
+          n4[i] = nd[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) a[i] = a_nxt[i];
+        if (k + 1 < K) load4<int32_t>(act + off + p.B, env0, p.B, a_nxt);  // one step ahead
+      }
+      float r[EPT];
+      uint8_t tm[EPT], tr[EPT];
+      int32_t ob[EPT];
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) {
+        const bool live = env0 + i < p.B;
+        const StepOut o = at_env_step<REPLAY>(p, lds, u[i], a[i], env0 + i, live, step, rsum, eps, lens);
+        r[i] = o.rew;
+        tm[i] = o.term;
+        tr[i] = o.trunc;
+        ob[i] = at_obs_idx(p, u[i]);
+        nst += live ? 1u : 0u;
+        if constexpr (CTRL)  // j % M; episode end: node 0
+          nd[i] = (o.term | o.trunc) ? (uint8_t)0 : (uint8_t)(jj[i] - (uint32_t)a[i] * (uint32_t)c.M);
+      }
+      if constexpr (CTRL) {
+        if (aout) store4<int32_t>(aout + off, env0, p.B, a);
+        if (nodes) store4<uint8_t>(nodes + off, env0, p.B, n4);
+      }
+      if (rew) store4<float>(rew + off, env0, p.B, r);
+      if (term) store4<uint8_t>(term + off, env0, p.B, tm);
+      if (trunc) store4<uint8_t>(trunc + off, env0, p.B, tr);
+      if (obs) store4<int32_t>(obs + off, env0, p.B, ob);
+    }
+    store4<uint32_t>(p.st, env0, p.B, u);
+    if constexpr (CTRL) store4<uint8_t>(c.node, env0, p.B, nd);
+  }
+  at_metrics(p, rsum, eps, lens, nst);
+}
+
+template <bool REPLAY>
+__global__ __launch_bounds__(TPB) void anttag_reset_idx(AtDev p, uint64_t step, int32_t* __restrict__ obs) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  stage_tables(p, lds);
+  __syncthreads();
+  for (int env = blockIdx.x * TPB + threadIdx.x; env < p.B; env += gridDim.x * TPB) {
+    const uint32_t u = draw_reset<REPLAY>(p, lds, env, step);
+    p.st[env] = u;
+    obs[env] = at_obs_idx(p, u);
+  }
+}
+
 __global__ void anttag_get_state(AtDev p, int32_t* ant, int32_t* tgt, int32_t* el) {
   const int env = blockIdx.x * TPB + threadIdx.x;
   if (env >= p.B) return;
@@ -299,9 +458,13 @@ __global__ void anttag_set_state(AtDev p, const int32_t* ant, const int32_t* tgt
 // ------------------------------------------------------------------ host backend ----
 struct AntTagBackend : EnvBackend {
   AtDev d{};
-  int grid = 1;
+  CtrlDev ctrl{};          // M == 0: no controller installed
+  bool obs_index = false;  // the scalar index obs (anttag_rollout_idx / anttag_reset_idx) instead of the vector
+  int grid = 1;            // blocks of the handle's open-loop rollout (and reset) kernel
+  int grid_ctrl = 1;       // blocks of the closed-loop rollout (index obs, philox)
+  int nslot = 1;           // metric slots: the larger of the two grids
   uint64_t philox_step = 0;
-  DevBuf b_tabs, b_st, b_slot;
+  DevBuf b_tabs, b_st, b_slot, b_cthr, b_cnode;
   DevErr derr;
   const int32_t* rp_choose = nullptr;
   const int32_t* rp_ant = nullptr;
@@ -331,17 +494,33 @@ struct AntTagBackend : EnvBackend {
     dd.rp_tgt = rp_tgt;
     return dd;
   }
+  int query(const char* key, int64_t* v) const override {
+    if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = 0;         // the table is read from global memory
+    else return EnvBackend::query(key, v);
+    return GP_OK;
+  }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(AtSlot) * grid, s));
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(AtSlot) * nslot, s));
+    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
     const AtDev dd = dev_for_launch();
     if (rng_mode == GP_RNG_REPLAY) {
       if (!rp_ant || !rp_tgt) {
         gp_set_error("anttag replay reset needs ant / target indices (gp_set_replay i0/i1)");
         return GP_E_STATE;
       }
-      hipLaunchKernelGGL(anttag_reset<true>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, (uint64_t)0, (int4*)obs);
+      if (obs_index)
+        hipLaunchKernelGGL(anttag_reset_idx<true>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, (uint64_t)0,
+                           (int32_t*)obs);
+      else
+        hipLaunchKernelGGL(anttag_reset<true>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, (uint64_t)0, (int4*)obs);
     } else {
-      hipLaunchKernelGGL(anttag_reset<false>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, philox_step, (int4*)obs);
+      if (obs_index)
+        hipLaunchKernelGGL(anttag_reset_idx<false>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, philox_step,
+                           (int32_t*)obs);
+      else
+        hipLaunchKernelGGL(anttag_reset<false>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, philox_step, (int4*)obs);
       ++philox_step;
     }
     GP_HIP_CHECK(hipGetLastError());
@@ -353,7 +532,7 @@ struct AntTagBackend : EnvBackend {
       gp_set_error("step() before reset()");
       return GP_E_STATE;
     }
-    if (((uintptr_t)obs & 15) != 0) {
+    if (!obs_index && ((uintptr_t)obs & 15) != 0) {  // (the index obs falls back to element-wise stores)
       gp_set_error("anttag: obs buffer must be 16-B aligned");
       return GP_E_INVALID;
     }
@@ -365,17 +544,61 @@ struct AntTagBackend : EnvBackend {
       }
       if (K > 1) return EnvBackend::rollout(K, act, obs, rew, term, trunc, s);
       timer.begin(s);
-      hipLaunchKernelGGL(anttag_rollout<true>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, K, (uint64_t)0,
-                         (const int32_t*)act, (int4*)obs, rew, term, trunc);
+      if (obs_index)
+        hipLaunchKernelGGL((anttag_rollout_idx<true, false>), dim3(grid), dim3(TPB), d.tab_bytes, s, dd, CtrlDev{}, K,
+                           (uint64_t)0, (const int32_t*)act, (int32_t*)obs, (int32_t*)nullptr, (uint8_t*)nullptr, rew,
+                           term, trunc);
+      else
+        hipLaunchKernelGGL(anttag_rollout<true>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, K, (uint64_t)0,
+                           (const int32_t*)act, (int4*)obs, rew, term, trunc);
       timer.end(s);
     } else {
       timer.begin(s);
-      hipLaunchKernelGGL(anttag_rollout<false>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, K, philox_step,
-                         (const int32_t*)act, (int4*)obs, rew, term, trunc);
+      if (obs_index)
+        hipLaunchKernelGGL((anttag_rollout_idx<false, false>), dim3(grid), dim3(TPB), d.tab_bytes, s, dd, CtrlDev{},
+                           K, philox_step, (const int32_t*)act, (int32_t*)obs, (int32_t*)nullptr, (uint8_t*)nullptr,
+                           rew, term, trunc);
+      else
+        hipLaunchKernelGGL(anttag_rollout<false>, dim3(grid), dim3(TPB), d.tab_bytes, s, dd, K, philox_step,
+                           (const int32_t*)act, (int4*)obs, rew, term, trunc);
       timer.end(s);
       philox_step += (uint64_t)K;
     }
     GP_HIP_CHECK(hipGetLastError());
+    return GP_OK;
+  }
+  // Closed-loop rollouts: the index obs in philox mode only (a controller table is indexed by a scalar obs, and its
+  // draws are stated against the philox step index).
+  int ctrl_supported(const char* what) const {
+    if (obs_index && rng_mode == GP_RNG_PHILOX) return GP_OK;
+    gp_set_error("%s: anttag runs controllers on the index obs (obs_index = 1) in GP_RNG_PHILOX only", what);
+    return GP_E_UNSUPPORTED;
+  }
+  int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
+  int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
+                         hipStream_t s) override {
+    if (int e = ctrl_supported("gp_rollout_controller")) return e;
+    if (!has_reset || !ctrl.M) {
+      gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
+                                                                        "(gp_set_controller)");
+      return GP_E_STATE;
+    }
+    timer.begin(s);
+    hipLaunchKernelGGL((anttag_rollout_idx<false, true>), dim3(grid_ctrl), dim3(TPB), d.tab_bytes, s, d, ctrl, K,
+                       philox_step, (const int32_t*)nullptr, (int32_t*)obs, act, nodes, rew, term, trunc);
+    timer.end(s);
+    philox_step += (uint64_t)K;
+    GP_HIP_CHECK(hipGetLastError());
+    return GP_OK;
+  }
+  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
+    if (int e = ctrl_supported("gp_controller_nodes")) return e;
+    if (!ctrl.M) {
+      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
+      return GP_E_STATE;
+    }
+    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
+    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
     return GP_OK;
   }
   int step(const void* act, void* obs, float* rew, uint8_t* term, uint8_t* trunc, hipStream_t s) override {
@@ -407,8 +630,8 @@ struct AntTagBackend : EnvBackend {
   }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<AtSlot> m(grid);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(AtSlot) * grid, hipMemcpyDeviceToHost));
+    std::vector<AtSlot> m(nslot);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(AtSlot) * nslot, hipMemcpyDeviceToHost));
     out[0] = out[1] = out[2] = out[3] = 0;
     for (const AtSlot& x : m) {
       out[0] += (double)x.episodes;
@@ -420,6 +643,44 @@ struct AntTagBackend : EnvBackend {
   }
 };
 
+// thr_host rows hold L = 5 M entries (M <= 8: L <= 40, below the 64 up to which j / M by inv_m is exact); L is no
+// multiple of 4 in general, so each uploaded row is padded to a multiple of 4 entries with 2^31 (never counted:
+// y < 2^31) and ctrl_search keeps its 16-B quads.
+int AntTagBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
+  if (int e = ctrl_supported("gp_set_controller")) return e;
+  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
+  if (!thr_host) {
+    ctrl = CtrlDev{};
+    int e;
+    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
+    return GP_OK;
+  }
+  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
+    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
+    return GP_E_INVALID;
+  }
+  const int L = NACT * n_nodes, Lp = (L + 3) & ~3;
+  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)Lp;
+  if (n > ((size_t)1 << 28)) {
+    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
+    return GP_E_INVALID;
+  }
+  std::vector<uint32_t> padded(n);
+  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L, Lp, padded.data())) return e;
+  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
+  int e;
+  if ((e = b_cthr.upload(padded)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
+  ctrl.thr = b_cthr.as<uint32_t>();
+  ctrl.node = b_cnode.as<uint8_t>();
+  ctrl.M = n_nodes;
+  ctrl.n_obs = n_obs;
+  ctrl.L = Lp;
+  ctrl.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
+  ctrl.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
+  ctrl.lds_off = -1;
+  return GP_OK;
+}
+
 int AntTagBackend::build(const gp_anttag_config* cfg) {
   const int N = cfg->size, nc = N * N;
   if (N < 2 || N > MAX_SIZE) {
@@ -428,6 +689,10 @@ int AntTagBackend::build(const gp_anttag_config* cfg) {
   }
   if (cfg->time_limit < 1 || cfg->time_limit > 65535) {
     gp_set_error("anttag: time_limit %d outside [1, 65535]", cfg->time_limit);
+    return GP_E_INVALID;
+  }
+  if (cfg->obs_index != 0 && cfg->obs_index != 1) {
+    gp_set_error("anttag: obs_index %d is neither 0 (vector obs) nor 1 (index obs)", cfg->obs_index);
     return GP_E_INVALID;
   }
   std::vector<uint8_t> cnt(nc, 0), list((size_t)nc * nc, 0);
@@ -471,18 +736,35 @@ int AntTagBackend::build(const gp_anttag_config* cfg) {
   d.time_limit = cfg->time_limit;
   d.r_tag = cfg->tag_reward;
   d.r_step = cfg->step_reward;
+  obs_index = cfg->obs_index == 1;
   obs_dtype = GP_DTYPE_I32;
-  obs_width = 4;
+  obs_width = obs_index ? 1 : 4;
   if ((e = b_st.alloc((size_t)B * 4 + 16))) return e;
   d.st = b_st.as<uint32_t>();
   hipDeviceProp_t prop;
   GP_HIP_CHECK(hipGetDeviceProperties(&prop, device));
   int occ = 0;
-  GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, anttag_rollout<false>, TPB, d.tab_bytes));
+  if (!obs_index) {
+    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, anttag_rollout<false>, TPB, d.tab_bytes));
+  } else if (rng_mode == GP_RNG_REPLAY) {
+    GP_HIP_CHECK(
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, anttag_rollout_idx<true, false>, TPB, d.tab_bytes));
+  } else {
+    GP_HIP_CHECK(
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, anttag_rollout_idx<false, false>, TPB, d.tab_bytes));
+  }
   grid = persistent_grid(d.ntiles, prop.multiProcessorCount, occ);
   persist_grid = grid;
   persist_occ = occ;
-  if ((e = b_slot.alloc(sizeof(AtSlot) * grid))) return e;
+  nslot = grid;
+  if (obs_index && rng_mode == GP_RNG_PHILOX) {  // the closed-loop kernel has its own register budget and grid
+    int occ_c = 0;
+    GP_HIP_CHECK(
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, anttag_rollout_idx<false, true>, TPB, d.tab_bytes));
+    grid_ctrl = persistent_grid(d.ntiles, prop.multiProcessorCount, occ_c);
+    nslot = std::max(grid, grid_ctrl);
+  }
+  if ((e = b_slot.alloc(sizeof(AtSlot) * nslot))) return e;
   d.mslot = b_slot.as<AtSlot>();
   if ((e = derr.alloc())) return e;
   d.derr = derr.ptr();

@@ -102,7 +102,7 @@ struct EnvBackend {
     return GP_E_UNSUPPORTED;
   }
   // Closed-loop rollouts (gp_set_controller / gp_rollout_controller / gp_controller_nodes): GRID in philox mode,
-  // ROCKSAMPLE.
+  // ROCKSAMPLE, ANTTAG with the index obs in philox mode.
   virtual int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
     gp_set_error("controllers are not supported by this env kind");
     return GP_E_UNSUPPORTED;

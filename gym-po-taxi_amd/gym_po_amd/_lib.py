@@ -58,7 +58,7 @@ class CRoomsConfig(ctypes.Structure):
 class AntTagConfig(ctypes.Structure):
     _fields_ = [("size", ctypes.c_int32), ("tag_radius2", ctypes.c_int32), ("visible_radius2", ctypes.c_int32),
                 ("min_start_dist2", ctypes.c_int32), ("time_limit", ctypes.c_int32),
-                ("tag_reward", ctypes.c_float), ("step_reward", ctypes.c_float)]
+                ("tag_reward", ctypes.c_float), ("step_reward", ctypes.c_float), ("obs_index", ctypes.c_int32)]
 
 
 class CarFlagConfig(ctypes.Structure):

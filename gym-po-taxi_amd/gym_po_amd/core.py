@@ -284,8 +284,8 @@ class NativeVecEnv:
 
     def set_controller(self, probs=None, thresholds=None):
         """Install the tabular controller of the closed-loop rollouts (FourRooms / ROOMS with a scalar obs in
-        rng_mode='philox', and RockSample, where A * M may not exceed 64), or remove it when both arguments are
-        None. `probs`: float [M, n_obs, A, M], the joint
+        rng_mode='philox', RockSample, where A * M may not exceed 64, and AntTagGridEnv with obs_type='index' in
+        rng_mode='philox'), or remove it when both arguments are None. `probs`: float [M, n_obs, A, M], the joint
         probability of (action, next node) given (node, obs), or [n_obs, A] for a memoryless policy; lowered by
         `controller.controller_thresholds`. `thresholds`: that uint32 [M, n_obs, A * M] table itself. n_obs is
         `single_observation_space.n`, A the action count, M <= 8. Every env's node becomes 0. Raises GymPoError for

@@ -2,10 +2,11 @@
 from .rooms import CRoomsEnv, MultistoryFourRoomsEnv, RoomsEnv
 from .extended_taxi import (EXTENDED_TAXI_MAP, TAXI_MAP, ExtendedHansenTaxiVecEnv, ExtendedTaxiVecEnv,
                             HansenTaxiVecEnv, TaxiVecEnv)
-from .ant_tag_grid import AntTagGridEnv
+from .ant_tag_grid import AntTagGridEnv, ant_tag_obs_index, ant_tag_obs_vector
 from .car_flag import CarVecEnv, DiscreteActionCarVecEnv
 from .rocksample import RockSample, rocksample_sensor_thresholds
 
 __all__ = ["RoomsEnv", "CRoomsEnv", "MultistoryFourRoomsEnv", "TaxiVecEnv", "HansenTaxiVecEnv",
            "ExtendedTaxiVecEnv", "ExtendedHansenTaxiVecEnv", "TAXI_MAP", "EXTENDED_TAXI_MAP", "AntTagGridEnv",
-           "CarVecEnv", "DiscreteActionCarVecEnv", "RockSample", "rocksample_sensor_thresholds"]
+           "ant_tag_obs_index", "ant_tag_obs_vector", "CarVecEnv", "DiscreteActionCarVecEnv", "RockSample",
+           "rocksample_sensor_thresholds"]

@@ -150,6 +150,12 @@ typedef struct gp_anttag_config {
   int32_t min_start_dist2; /* squared minimum start separation                                 */
   int32_t time_limit;
   float tag_reward, step_reward;
+  int32_t obs_index;       /* 0: obs = int32 [ant y, ant x, target y, target x] (GP_DTYPE_I32, width 4), the target
+                              (-1, -1) unless visible. 1: obs = the scalar int32 (width 1)
+                              ant_cell * (nc + 1) + (visible ? target_cell : nc), nc = size * size, cell = y * size + x:
+                              the same information (a bijection onto the vectors that occur), in [0, nc * (nc + 1)).
+                              Transitions, draws, rewards, flags, state and metrics do not depend on it. The index
+                              obs has no buffer alignment requirement; the vector obs needs 16-B aligned buffers. */
 } gp_anttag_config;
 
 /* Car-Flag (car_flag.py:50-144, :286-303). Observation: GP_DTYPE_F32, width 3 (position, velocity, direction). */
@@ -241,8 +247,8 @@ int gp_plan_run(gp_plan* plan);
 void gp_plan_destroy(gp_plan* plan);
 
 /* ---- closed-loop rollouts: a tabular finite-state controller evaluated inside the rollout kernel ----
- * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), and ROCKSAMPLE (either obs); every other
- * kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
+ * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), ROCKSAMPLE (either obs), and ANTTAG with the
+ * index obs (obs_index = 1) in GP_RNG_PHILOX; every other kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
  * one step() per action.)
  *
  * The controller has M = n_nodes nodes (1..8; M = 1 is a memoryless policy obs -> action distribution). With A the
@@ -263,6 +269,8 @@ void gp_plan_destroy(gp_plan* plan);
  * A = 5 + n_rocks need not be a multiple of 4: thr_host rows hold exactly L = A * M entries, and the library pads each
  * uploaded row to a multiple of 4 entries with 2^31, which no y reaches. A * M > 64 is GP_E_INVALID (the j / M
  * multiply is exact below 64).
+ * ANTTAG: the obs is the index obs of the state word; the env draws carry 0x616e7431. A = 5, so L = 5 M <= 40 and rows
+ * are padded to 16-B quads as ROCKSAMPLE's are. n_obs is the caller's (the obs space has size^2 * (size^2 + 1) values).
  *
  * gp_set_controller validates the table, uploads it synchronously and zeroes every node; thr_host = NULL removes the
  * controller. The nodes (uint8 [B], handle state) persist across calls; gp_reset zeroes them; gp_step / gp_rollout
@@ -325,7 +333,8 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * "fused_tiles_per_block", "fused_staged" (1 = LDS-staged outputs + store waves),
  * "fused_tile_envs", "philox_step" (GP_RNG_PHILOX: the counter's step index that the next reset / step draws
  * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
- * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE: always 0). Unknown keys return
+ * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE, ANTTAG: always 0); ROCKSAMPLE
+ * and ANTTAG answer the last three too. Unknown keys return
  * GP_E_INVALID. */
 int gp_query(const gp_env* env, const char* key, int64_t* value);
 /* ---- the normal sampler of rng_mode=philox (C-ROOMS noise), diagnostics ----
