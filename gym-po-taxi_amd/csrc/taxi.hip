@@ -144,6 +144,7 @@ __device__ __forceinline__ StepOut taxi_env_step(const TaxiDev& p, const uint8_t
   StepOut o;
   o.rew = goal ? p.r_goal : (bad ? p.r_bad : p.r_any);
   o.term = (nd == (uint32_t)p.num_passengers) ? 1 : 0;
+  nd = min(nd, 15u);                          // the 4-bit field saturates (set_state can store 15): never into elapsed
   o.trunc = (el > (uint32_t)p.time_limit) ? 1 : 0;
   if (!live) return o;                        // padding lane of a ragged batch: no draws, no metrics
   rsum += o.rew;
@@ -856,7 +857,7 @@ __global__ __launch_bounds__(NP_TPB) void taxi_np_kernel(TaxiDev p, TaxiNpDev q,
           eps += 1u;
           lens += el;
         }
-        p.st[env] = s | (nd << 12) | (min(el, 0xFFFFu) << 16);
+        p.st[env] = s | (min(nd, 15u) << 12) | (min(el, 0xFFFFu) << 16);  // nd saturates (as taxi_env_step)
       }
       uint32_t rtc, rrs, ttc, trs;
       np_tile_scan(ftc, frs, sh.wcnt, rtc, rrs, ttc, trs);
@@ -1030,7 +1031,7 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass1(TaxiDev p, TaxiNpDev q, Np
         eps += 1u;
         lens += el;
       }
-      u[i] = s | (nd << 12) | (min(el, 0xFFFFu) << 16);
+      u[i] = s | (min(nd, 15u) << 12) | (min(el, 0xFFFFu) << 16);  // nd saturates (as taxi_env_step)
     }
     st4_u32(reinterpret_cast<uint32_t*>(rew + off), env0, p.B,
             {__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])});

@@ -292,7 +292,11 @@ int gp_controller_nodes(gp_env* env, uint8_t* get, const uint8_t* set, void* str
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
  * mask, elapsed. CARFLAG: s f32[B,3]
  * (position, velocity, direction), elapsed i32[B], heavens f32[B] (+-1), priests f32[B] (+-0.5; set takes
- * both by sign). */
+ * both by sign).
+ * TAXI packs n_dropoffs into 4 bits: gp_set_state clamps it to [0, 15] and a goal move from 15 leaves it at 15
+ * (the reference counts on without bound). terminated is decided on the unsaturated count, so s, elapsed, the
+ * rewards and both flags follow the reference for every count gp_set_state can store; only the count read back
+ * by gp_get_state stops at 15. An episode started by reset never gets there (num_passengers <= 15 ends it). */
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream);
 int gp_set_state(gp_env* env, const void* a, const void* b, const void* c, const void* d, void* stream);
 

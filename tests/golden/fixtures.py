@@ -39,6 +39,43 @@ def load_case(name):
     return meta, data
 
 
+def load_table(name):
+    """A `taxi_table` case (make_golden.py TAXI_TABLES): (index entry, recorded arrays)."""
+    meta = load_index()["taxi_table"][name]
+    return meta, np.load(os.path.join(GOLDEN_DIR, meta["file"]), allow_pickle=False)
+
+
+def taxi_table_replicas(meta):
+    """The (elapsed, n_dropoffs_completed) replicas of a taxi_table case, in row order."""
+    tl, npass = meta["kwargs"]["time_limit"], meta["kwargs"]["num_passengers"]
+    return [(e, n) for e in (0, tl - 1, tl) for n in range(npass)]
+
+
+def taxi_table_inputs(meta):
+    """Regenerate the rows a taxi_table case was recorded on: (s, action, elapsed, n_dropoffs), int64 [B].
+    Row order: replica-major, then every state 0..ns-1, then the actions -5..4."""
+    ns = meta["ns"]
+    s, a = np.meshgrid(np.arange(ns), np.arange(-5, 5), indexing="ij")
+    reps = taxi_table_replicas(meta)
+    s, a = np.tile(s.ravel(), len(reps)), np.tile(a.ravel(), len(reps))
+    e = np.repeat([r[0] for r in reps], ns * 10)
+    n = np.repeat([r[1] for r in reps], ns * 10)
+    assert s.size == meta["num_envs"]
+    return s, a, e, n
+
+
+def taxi_table_counts(meta, a, rew, term, trunc):
+    """Per-replica counts of the rare rows of one table step, from the step's own outputs: a pickup is the only
+    action-4 row paid reward_any; a task completion is a goal row whose episode goes on."""
+    kw = meta["kwargs"]
+    rew, term, trunc = np.asarray(rew), np.asarray(term).astype(bool), np.asarray(trunc).astype(bool)
+    goal, bad = rew == np.float32(kw["reward_goal"]), rew == np.float32(kw["reward_bad"])
+    rows = dict(goal=goal, bad=bad, pick=(np.asarray(a) == 4) & (rew == np.float32(kw["reward_any"])), term=term,
+                trunc=trunc, task=goal & ~(term | trunc))
+    n = len(taxi_table_replicas(meta))
+    return {k: [int(x) for x in v.reshape(n, -1).sum(-1)] for k, v in rows.items()}
+
+
 def step_actions(meta):
     """Regenerate the action sequence a fixture was recorded with."""
     rng = np.random.default_rng(meta["action_seed"])

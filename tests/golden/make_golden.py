@@ -8,6 +8,9 @@ Every case: construct the reference env with the recorded kwargs, reset(seed=see
 with actions regenerated from `default_rng(action_seed)` (fixtures.step_actions). Recorded per
 step: obs, reward, terminated, truncated (full arrays for small cases, per-step digests for large
 ones), plus the final internal state and the final PCG64 state of the env's Generator.
+
+The `taxi_table` group (TAXI_TABLES, files taxi_table_*.npz, `python tests/golden/make_golden.py taxi_table`) is one
+reference step over every (state, action) row of a Taxi map instead of a trajectory: see run_taxi_table.
 """
 import os
 import sys
@@ -187,6 +190,64 @@ def taxi_reset_histogram(m, n_samples=2_000_000, seed=123):
     return dict(file="taxi_reset_hist.npz", n_samples=n_samples, seed=seed, numpy=np.__version__)
 
 
+# ---- Taxi one-step tables: every (state, action) row of a map, stepped once by the reference ----
+# name: (ctor kwargs, seed). Dyadic rewards (sums of them are exact in float32); two passengers with time_limit 3 so
+# that the elapsed replicas {0, tl - 1, tl} and the dropoff replicas {0, 1} reach task completion, termination and
+# truncation on the same rows. ("R G",) has the plain width 18 (no multiple of 4), ("RG",) 12 (a multiple of 4, not
+# of 16): the one-hot byte and 4-byte streams.
+_TBL_REW = dict(reward_goal=2.0, reward_bad=-1.0, reward_any=-0.25)
+_TBL_2P = dict(num_passengers=2, time_limit=3, **_TBL_REW)
+_TBL_1P = dict(num_passengers=1, time_limit=200, **_TBL_REW)
+TAXI_TABLES = {
+    "taxi_table_taxi_plain_2p": (dict(map="TAXI", **_TBL_2P), 1),
+    "taxi_table_taxi_hansen_2p": (dict(map="TAXI", hansen_obs=True, **_TBL_2P), 2),
+    "taxi_table_ext_plain_2p": (dict(map="EXTENDED", **_TBL_2P), 3),
+    "taxi_table_ext_hansen_2p": (dict(map="EXTENDED", hansen_obs=True, **_TBL_2P), 4),
+    "taxi_table_taxi_plain_1p": (dict(map="TAXI", **_TBL_1P), 5),
+    "taxi_table_taxi_hansen_1p": (dict(map="TAXI", hansen_obs=True, **_TBL_1P), 6),
+    "taxi_table_r_g_plain_2p": (dict(map=["R G"], **_TBL_2P), 7),
+    "taxi_table_rg_plain_2p": (dict(map=["RG"], **_TBL_2P), 8),
+}
+
+
+def _rng6(gen):
+    st = gen.bit_generator.state
+    return np.array([st["state"]["state"] >> 64, st["state"]["state"] & ((1 << 64) - 1),
+                     st["state"]["inc"] >> 64, st["state"]["inc"] & ((1 << 64) - 1),
+                     st["has_uint32"], st["uinteger"]], dtype=np.uint64)
+
+
+def run_taxi_table(m, name, spec):
+    """reset(seed), overwrite s / elapsed / n_dropoffs_completed with the table's rows (fixtures.taxi_table_inputs),
+    one step. Recorded: the four outputs, the post-step state (the reference's own reset and passenger / destination
+    draws included), the PCG64 state before and after the step, and the per-replica counts of the rare rows."""
+    from fixtures import taxi_table_counts, taxi_table_inputs
+    kw, seed = spec
+    ctor = dict(kw)
+    ctor.pop("map")
+    if kw["map"] == "EXTENDED":
+        ctor["map"] = m["extended_taxi"].EXTENDED_TAXI_MAP
+    elif kw["map"] != "TAXI":
+        ctor["map"] = tuple(kw["map"])
+    probe = m["extended_taxi"].TaxiVecEnv(1, **ctor)
+    meta = dict(kind="taxi_table", kwargs=kw, seed=seed, ns=int(probe.ns), n_obs=int(probe.no),
+                nlocs=int(probe.nlocs), numpy=np.__version__, file=f"{name}.npz")
+    meta["num_envs"] = B = 10 * meta["ns"] * 3 * kw["num_passengers"]
+    s, a, e, n = taxi_table_inputs(meta)
+    env = m["extended_taxi"].TaxiVecEnv(B, **ctor)
+    env.reset(seed=seed)
+    pre = _rng6(env.np_random)
+    env.s, env.elapsed, env.n_dropoffs_completed = s.copy(), e.copy(), n.astype(float)
+    o, r, d, tr, _ = env.step(a)
+    assert r.dtype == np.float32 and np.asarray(o).max() < 32768 and env.s.max() < 32768
+    meta["counts"] = taxi_table_counts(meta, a, r, d, tr)
+    np.savez_compressed(os.path.join(HERE, meta["file"]), obs=np.asarray(o).astype(np.int16), rew=r,
+                        term=np.asarray(d, bool), trunc=np.asarray(tr, bool), s=env.s.astype(np.int16),
+                        elapsed=env.elapsed.astype(np.int16), n_dropoffs=env.n_dropoffs_completed.astype(np.int8),
+                        pre_rng_state=pre, rng_state=_rng6(env.np_random))
+    return meta
+
+
 def main():
     import json
     prefix = sys.argv[1] if len(sys.argv) > 1 else ""
@@ -201,6 +262,12 @@ def main():
         t0 = time.time()
         index["cases"][name] = run_case(m, name, spec)
         print(f"{name}: {time.time() - t0:.1f}s", flush=True)
+    for name, spec in TAXI_TABLES.items():
+        if not name.startswith(prefix):
+            continue
+        t0 = time.time()
+        index.setdefault("taxi_table", {})[name] = run_taxi_table(m, name, spec)
+        print(f"{name}: {time.time() - t0:.1f}s {index['taxi_table'][name]['counts']}", flush=True)
     if prefix in ("", "taxi_reset_hist"):
         t0 = time.time()
         index["taxi_reset_hist"] = taxi_reset_histogram(m)

@@ -15,6 +15,8 @@ import torch  # noqa: E402
 
 from gym_po_amd import HansenTaxiVecEnv  # noqa: E402
 
+NPG_MIN_ENVS = 1024  # csrc/taxi.hip: at or below, the one-workgroup kernel (unless NPG_MIN overrides it)
+
 
 def rate(mode, B, K=None, reps=3):
     K = K or (50 if B <= 65536 else 10)
@@ -38,7 +40,7 @@ def rate(mode, B, K=None, reps=3):
     m = env.metrics()
     return {"mode": mode, "num_envs": B, "steps": K * reps, "us_per_step": dt / (K * reps) * 1e6,
             "env_steps_per_s": B * K * reps / dt, "episodes_so_far": m["episodes"], "reset_s": reset_s,
-            "path": ("grid-wide" if B > knobs.get("taxi_npg_min", 4096) else "one workgroup") if mode == "numpy" else "-"}
+            "path": ("grid-wide" if B > knobs.get("taxi_npg_min", NPG_MIN_ENVS) else "one workgroup") if mode == "numpy" else "-"}
 
 
 if __name__ == "__main__":
