@@ -2674,10 +2674,9 @@ __global__ __launch_bounds__(TPB) void grid_rollout_counter(GridDev p, int K, ui
 // state in registers. The row is read from global memory (L1/L2: ROOMS Hansen-8 tables are 74 KB-4.7 MB, FourRooms
 // Hansen-8 1.9 MB and up), or, CL, from a copy of the table staged in LDS behind the env's tables when both are small
 // (FourRooms Hansen-4: 6.5 KB with M = 1, 26 KB with M = 2). Rows are 16-B aligned: L = nact * M is a multiple of 4.
-// CTRL_TAG, CtrlDev and the row search ctrl_search: gp_ctrl.h (shared with rocksample.hip).
-// Largest dynamic LDS per block (env tables + controller table) with the controller staged: 5 blocks per CU stay
-// resident, more than the 4 a 2^20-env launch puts there.
-constexpr int CTRL_LDS_BUDGET = 32 * 1024;
+// CTRL_TAG, CtrlDev, the row search ctrl_search and the staging budget CTRL_LDS_BUDGET: gp_ctrl.h (shared with
+// rocksample.hip, anttag.hip and taxi.hip). At that budget 5 blocks per CU stay resident, more than the 4 a 2^20-env
+// launch puts there.
 
 template <int OK, bool LT = false, bool CL = false>
 __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDev c, int K, uint64_t step0,

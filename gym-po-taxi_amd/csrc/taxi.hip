@@ -23,12 +23,14 @@
 // Kernels: one persistent, grid-stride rollout kernel (tables staged in LDS once per block, 1024-env
 // tiles, K steps per tile with the state in registers) for both scalar and one-hot observations; the
 // one-hot rows (uint8 [B, n_obs], 320 B/env for Hansen) are written as a wave-contiguous stream of
-// 16-B chunks so every store instruction covers 1 KB of consecutive bytes.
+// 16-B chunks so every store instruction covers 1 KB of consecutive bytes. taxi_rollout_ctrl is the same loop with
+// the action drawn on the device by a tabular finite-state controller (gp_rollout_controller; Hansen obs, philox).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "gp_ctrl.h"
 #include "gp_internal.h"
 #include "gp_libm.h"
 
@@ -316,6 +318,121 @@ __global__ __launch_bounds__(TPB) void taxi_rollout(TaxiDev p, int K, uint64_t s
       }
     }
     st4_u32(p.st, env0, p.B, u);
+  }
+  taxi_metrics(p, rsum, eps, lens, nst);
+}
+
+// ---- the closed-loop rollout: taxi_rollout<OH, false> with the action drawn on the device ----
+// gp_rollout_controller (semantics in include/gym_po_amd.h; CtrlDev, CTRL_TAG and ctrl_search: gp_ctrl.h): per
+// env-step one more Philox block, tagged CTRL_TAG, picks j = action * M + next_node from the threshold row of
+// (node, obs). The obs index that conditions step k stays in registers: looked up once per tile before the first step
+// and once after each transition, where the same value is the step's obs output (scalar, or the hot index of the
+// one-hot row). Same geometry as the open loop (persistent grid, 1,024-env tiles, 4 consecutive envs per thread, the
+// packed state in registers across the K steps); the node byte travels with the state. CL: the controller table is
+// staged in the dynamic LDS behind the env's tables (c.lds_off = p.tab_bytes; 16-B granules, rows read as 16-B quads);
+// otherwise its rows are read from global memory. Every output pointer may be null: block-uniform branches.
+template <int OH, bool CL>
+__global__ __launch_bounds__(TPB) void taxi_rollout_ctrl(TaxiDev p, CtrlDev c, int K, uint64_t step0,
+                                                         void* __restrict__ obs, int32_t* __restrict__ act,
+                                                         uint8_t* __restrict__ nodes, float* __restrict__ rew,
+                                                         uint8_t* __restrict__ term, uint8_t* __restrict__ trunc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  __shared__ uint16_t s_hot[WAVES][256];
+  stage_tables(p, lds);
+  if constexpr (CL) {
+    const uint4* src = (const uint4*)c.thr;
+    uint4* dst = (uint4*)(lds + c.lds_off);
+    for (int i = threadIdx.x; i < c.bytes / 16; i += TPB) dst[i] = src[i];
+  }
+  __syncthreads();
+  const uint32_t* cthr = CL ? reinterpret_cast<const uint32_t*>(lds + c.lds_off) : c.thr;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float rsum = 0.f;
+  uint32_t eps = 0, lens = 0, nst = 0;
+  const uint16_t* obs_of = l_obs(lds, p);
+  const uint32_t lreal = (uint32_t)(NACT * c.M);  // entries of a row before its padding to 16-B quads
+  for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
+    const int env0 = tile * EPB + threadIdx.x * EPT;
+    uint32_t u[4], h[4];
+    uint8_t nd[4];
+    ld4_u32(p.st, env0, p.B, u);
+    const bool nq = quad_ok(c.node, env0, p.B, 1);
+    if (nq) {
+      const uint32_t q = *reinterpret_cast<const uint32_t*>(c.node + env0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) nd[i] = (uint8_t)(q >> (8 * i));
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) nd[i] = env0 + i < p.B ? c.node[env0 + i] : (uint8_t)0;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
+        if (env0 + i < p.B) atomicOr(p.derr, GP_DERR_CTRL);
+        nd[i] = (uint8_t)(c.M - 1);
+      }
+      h[i] = obs_of[u[i] & 0xFFFu];  // the obs of the state the env is in (what the reset, or the last step, emitted)
+    }
+    for (int k = 0; k < K; ++k) {
+      const size_t off = (size_t)k * p.B;
+      const uint64_t step = step0 + (uint64_t)k;
+      uint32_t a4[4];
+      uint8_t n4[4], tm[4], tr[4];
+      float r[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int env = env0 + i;
+        const bool live = env < p.B;
+        const uint32_t y = live ? philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG, p.key0,
+                                                p.key1).x[0] >> 1
+                                : 0u;
+        uint32_t o = h[i];
+        if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
+          if (live) atomicOr(p.derr, GP_DERR_CTRL);
+          o = (uint32_t)c.n_obs - 1u;
+        }
+        // (a table holds at most 2^28 entries: the entry index fits 32 bits)
+        const uint32_t* row = cthr + ((uint32_t)nd[i] * (uint32_t)c.n_obs + o) * (uint32_t)c.L;
+        const uint32_t j = min(ctrl_search(row, c.L, y), lreal - 1u);  // never a padding entry
+        const uint32_t a = (j * c.inv_m) >> 16;                         // j / M
+        n4[i] = nd[i];
+        a4[i] = a;
+        const StepOut so = taxi_env_step<false>(p, lds, u[i], (int)a, env, live, step, rsum, eps, lens);
+        r[i] = so.rew;
+        tm[i] = so.term;
+        tr[i] = so.trunc;
+        nd[i] = (so.term | so.trunc) ? (uint8_t)0 : (uint8_t)(j - a * (uint32_t)c.M);  // j % M; episode end: node 0
+        h[i] = obs_of[u[i] & 0xFFFu];
+        nst += live ? 1u : 0u;
+      }
+      if (act) st4_u32(reinterpret_cast<uint32_t*>(act + off), env0, p.B, a4);
+      if (nodes) st4_u8(nodes + off, env0, p.B, n4);
+      if (rew)
+        st4_u32(reinterpret_cast<uint32_t*>(rew + off), env0, p.B,
+                {__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])});
+      if (term) st4_u8(term + off, env0, p.B, tm);
+      if (trunc) st4_u8(trunc + off, env0, p.B, tr);
+      if (obs) {
+        if constexpr (OH == 0) {
+          st4_u32(reinterpret_cast<uint32_t*>(obs) + off, env0, p.B, h);
+        } else {
+          const int we0 = tile * EPB + wid * 256;  // first env of this wave
+          const int n = min(256, p.B - we0);
+          if (n > 0)
+            write_onehot_wave<OH>((uint8_t*)obs + (off + (size_t)we0) * (size_t)p.n_obs, n, p.n_obs, s_hot[wid], h,
+                                  lane);
+        }
+      }
+    }
+    st4_u32(p.st, env0, p.B, u);
+    if (nq) {
+      *reinterpret_cast<uint32_t*>(c.node + env0) =
+          (uint32_t)nd[0] | ((uint32_t)nd[1] << 8) | ((uint32_t)nd[2] << 16) | ((uint32_t)nd[3] << 24);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (env0 + i < p.B) c.node[env0 + i] = nd[i];
+    }
   }
   taxi_metrics(p, rsum, eps, lens, nst);
 }
@@ -1324,11 +1441,16 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass2(TaxiDev p, TaxiNpDev q, Np
 // ------------------------------------------------------------------ host backend ----
 struct TaxiBackend : EnvBackend {
   TaxiDev d{};
-  int grid = 1;                 // persistent grid size (= metric slots)
+  int grid = 1;                 // persistent grid size of the open-loop rollout (and reset) kernel
+  int grid_ctrl = 1;            // persistent grid size of the closed-loop rollout (set_controller decides it)
+  int nslot = 1;                // metric slots: every block either grid can have
+  int cus = 1, bpc_knob = 0;    // CUs of the device; the persist_bpc knob as gp_create read it
   int one_hot = 0;
+  bool hansen_obs = false;      // obs_kind == GP_OBS_HANSEN (the obs closed-loop rollouts condition on)
+  CtrlDev ctrl{};               // M == 0: no controller installed
   uint64_t philox_step = 0;
   std::vector<double> law;      // P(start state = valid[k])
-  DevBuf b_tabs, b_st, b_slot;
+  DevBuf b_tabs, b_st, b_slot, b_cthr, b_cnode;
   DevErr derr;
   const int32_t* rp_state = nullptr;
   const int32_t* rp_pd = nullptr;
@@ -1365,6 +1487,76 @@ struct TaxiBackend : EnvBackend {
     return derr.clear();
   }
   int check() override { return derr.check("taxi"); }
+  int query(const char* key, int64_t* v) const override {
+    if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
+    else if (!strcmp(key, "controller_blocks")) *v = ctrl.M ? grid_ctrl : 0;    // blocks of the closed-loop rollout
+    else return EnvBackend::query(key, v);
+    return GP_OK;
+  }
+  // Closed-loop rollouts: the Hansen obs in philox mode (the controller's draws are stated against the philox step
+  // index). The raw-state obs (GP_OBS_TABLE) is refused only because nothing pins it yet: the kernel conditions on
+  // obs_of[s] whichever table that is, so lifting it is dropping the `hansen_obs` test below.
+  int ctrl_supported(const char* what) const {
+    if (rng_mode != GP_RNG_PHILOX) {
+      gp_set_error("%s: taxi runs controllers in GP_RNG_PHILOX only, not in rng_mode %s", what,
+                   rng_mode == GP_RNG_NUMPY ? "numpy" : "replay");
+      return GP_E_UNSUPPORTED;
+    }
+    if (!hansen_obs) {
+      gp_set_error("%s: taxi runs controllers on the Hansen obs (GP_OBS_HANSEN) only, not on the raw-state obs "
+                   "(GP_OBS_TABLE)", what);
+      return GP_E_UNSUPPORTED;
+    }
+    return GP_OK;
+  }
+  int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
+  template <bool CL>
+  void launch_ctrl(int cs, int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
+                   hipStream_t s) {
+    const dim3 g((unsigned)grid_ctrl), b(TPB);
+    const size_t lds = (size_t)d.tab_bytes + (CL ? (size_t)ctrl.bytes : 0);
+    if (!one_hot)
+      hipLaunchKernelGGL((taxi_rollout_ctrl<0, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+                         trunc);
+    else if (cs == 16)
+      hipLaunchKernelGGL((taxi_rollout_ctrl<16, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+                         trunc);
+    else if (cs == 4)
+      hipLaunchKernelGGL((taxi_rollout_ctrl<4, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+                         trunc);
+    else
+      hipLaunchKernelGGL((taxi_rollout_ctrl<1, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+                         trunc);
+  }
+  int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
+                         hipStream_t s) override {
+    if (int e = ctrl_supported("gp_rollout_controller")) return e;
+    if (!has_reset || !ctrl.M) {
+      gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
+                                                                        "(gp_set_controller)");
+      return GP_E_STATE;
+    }
+    const int cs = one_hot && obs ? chunk_size(obs, K) : 16;  // (no obs plane: no one-hot stream runs)
+    timer.begin(s);
+    if (ctrl.lds_off >= 0) launch_ctrl<true>(cs, K, obs, act, nodes, rew, term, trunc, s);
+    else launch_ctrl<false>(cs, K, obs, act, nodes, rew, term, trunc, s);
+    timer.end(s);
+    GP_HIP_CHECK(hipGetLastError());
+    philox_step += (uint64_t)K;
+    return GP_OK;
+  }
+  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
+    if (int e = ctrl_supported("gp_controller_nodes")) return e;
+    if (!ctrl.M) {
+      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
+      return GP_E_STATE;
+    }
+    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
+    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
+    return GP_OK;
+  }
   int set_rng_state(const RngHost& r) override {
     if (rng_mode != GP_RNG_NUMPY) {
       gp_set_error("taxi: the PCG64 stream is used on the device only with rng_mode numpy");
@@ -1473,7 +1665,8 @@ struct TaxiBackend : EnvBackend {
     else hipLaunchKernelGGL((taxi_reset<1, REPLAY>), g, b, lds, s, dd, step, obs);
   }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(TaxiSlot) * grid, s));
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(TaxiSlot) * nslot, s));
+    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
     const int cs = chunk_size(obs, 1);
     if (rng_mode == GP_RNG_NUMPY) {
       launch_np(0, nullptr, obs, nullptr, nullptr, nullptr, s);
@@ -1540,8 +1733,8 @@ struct TaxiBackend : EnvBackend {
   }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<TaxiSlot> m(grid);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(TaxiSlot) * grid, hipMemcpyDeviceToHost));
+    std::vector<TaxiSlot> m(nslot);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(TaxiSlot) * nslot, hipMemcpyDeviceToHost));
     out[0] = out[1] = out[2] = out[3] = 0;
     for (const TaxiSlot& x : m) {
       out[0] += (double)x.episodes;
@@ -1738,7 +1931,13 @@ int TaxiBackend::build(const gp_taxi_config* cfg) {
   grid = persistent_grid(d.ntiles, prop.multiProcessorCount, occ);
   persist_grid = grid;
   persist_occ = occ;
-  if (int e = b_slot.alloc(sizeof(TaxiSlot) * grid)) return e;
+  // The closed-loop kernel gets a grid of its own once a table is installed (set_controller: its dynamic LDS depends
+  // on the table): the slots cover the largest either grid can be (8 blocks per CU, or the knob's).
+  cus = prop.multiProcessorCount;
+  bpc_knob = gp_debug_knobs().persist_bpc;
+  hansen_obs = cfg->obs_kind == GP_OBS_HANSEN;
+  nslot = std::max(grid, std::max(1, std::min((int)d.ntiles, cus * (bpc_knob > 0 ? bpc_knob : 8))));
+  if (int e = b_slot.alloc(sizeof(TaxiSlot) * nslot)) return e;
   d.mslot = b_slot.as<TaxiSlot>();
   if (int e = derr.alloc()) return e;
   d.derr = derr.ptr();
@@ -1748,6 +1947,59 @@ int TaxiBackend::build(const gp_taxi_config* cfg) {
   }
   if (rng_mode == GP_RNG_NUMPY)
     if (int e = np_build(valid)) return e;
+  return GP_OK;
+}
+
+// thr_host rows hold L = 5 M entries (M <= 8: L <= 40, below the 64 up to which j / M by inv_m is exact); L is no
+// multiple of 4 in general, so each uploaded row is padded to a multiple of 4 entries with 2^31 (never counted:
+// y < 2^31) and ctrl_search keeps its 16-B quads. The table is staged in LDS behind the env's tables when both fit
+// CTRL_LDS_BUDGET (knob ctrl_lds_max, at most 60 KB: with the 2 KB of static LDS a launch stays below 64 KB), and the
+// closed-loop kernel's persistent grid is sized from its occupancy at that dynamic-LDS size.
+int TaxiBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
+  if (int e = ctrl_supported("gp_set_controller")) return e;
+  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
+  if (!thr_host) {
+    ctrl = CtrlDev{};
+    int e;
+    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
+    return GP_OK;
+  }
+  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
+    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
+    return GP_E_INVALID;
+  }
+  const int L = NACT * n_nodes, Lp = (L + 3) & ~3;
+  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)Lp;
+  if (n > ((size_t)1 << 28)) {
+    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
+    return GP_E_INVALID;
+  }
+  std::vector<uint32_t> padded(n);
+  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L, Lp, padded.data())) return e;
+  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
+  int e;
+  if ((e = b_cthr.upload(padded)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
+  CtrlDev c{};
+  c.thr = b_cthr.as<uint32_t>();
+  c.node = b_cnode.as<uint8_t>();
+  c.M = n_nodes;
+  c.n_obs = n_obs;
+  c.L = Lp;
+  c.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
+  c.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
+  const int knob = gp_debug_knobs().ctrl_lds_max;
+  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
+  const bool staged = (size_t)d.tab_bytes + n * sizeof(uint32_t) <= budget;
+  c.lds_off = staged ? d.tab_bytes : -1;
+  const size_t lds = (size_t)d.tab_bytes + (staged ? n * sizeof(uint32_t) : 0);
+  int occ = 0;
+  using Kern = void (*)(TaxiDev, CtrlDev, int, uint64_t, void*, int32_t*, uint8_t*, float*, uint8_t*, uint8_t*);
+  const Kern kern = staged ? (one_hot ? taxi_rollout_ctrl<16, true> : taxi_rollout_ctrl<0, true>)
+                           : (one_hot ? taxi_rollout_ctrl<16, false> : taxi_rollout_ctrl<0, false>);
+  GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, TPB, lds));
+  const int bpc = bpc_knob > 0 ? bpc_knob : std::min(std::max(occ, 1), 8);  // as persistent_grid, the knob as created
+  grid_ctrl = std::max(1, std::min(std::min((int)d.ntiles, cus * bpc), nslot));  // never past the metric slots
+  ctrl = c;
   return GP_OK;
 }
 

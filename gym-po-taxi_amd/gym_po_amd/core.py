@@ -282,14 +282,21 @@ class NativeVecEnv:
             raise _lib.GymPoError(f"{_lib.LIB_PATH} has no {name}: closed-loop rollouts need a current build")
         return fn
 
+    def _controller_n_obs(self):
+        """The number of scalar observations a controller table must cover (None: not checked on the host). Envs whose
+        observation space does not carry it as `.n` (a one-hot encoding of a scalar obs) override this."""
+        return getattr(getattr(self, "single_observation_space", None), "n", None)
+
     def set_controller(self, probs=None, thresholds=None):
         """Install the tabular controller of the closed-loop rollouts (FourRooms / ROOMS with a scalar obs in
-        rng_mode='philox', RockSample, where A * M may not exceed 64, and AntTagGridEnv with obs_type='index' in
-        rng_mode='philox'), or remove it when both arguments are None. `probs`: float [M, n_obs, A, M], the joint
-        probability of (action, next node) given (node, obs), or [n_obs, A] for a memoryless policy; lowered by
-        `controller.controller_thresholds`. `thresholds`: that uint32 [M, n_obs, A * M] table itself. n_obs is
-        `single_observation_space.n`, A the action count, M <= 8. Every env's node becomes 0. Raises GymPoError for
-        a table that does not fit the env or is not monotone up to 2^31, and for envs without closed-loop rollouts."""
+        rng_mode='philox', RockSample, where A * M may not exceed 64, AntTagGridEnv with obs_type='index' in
+        rng_mode='philox', and TaxiVecEnv with hansen_obs=True in rng_mode='philox', scalar or one-hot: the table is
+        indexed by the scalar Hansen obs either way), or remove it when both arguments are None. `probs`: float
+        [M, n_obs, A, M], the joint probability of (action, next node) given (node, obs), or [n_obs, A] for a
+        memoryless policy; lowered by `controller.controller_thresholds`. `thresholds`: that uint32
+        [M, n_obs, A * M] table itself. n_obs is `single_observation_space.n` (a one-hot Taxi's row width `no`), A the
+        action count, M <= 8. Every env's node becomes 0. Raises GymPoError for a table that does not fit the env or
+        is not monotone up to 2^31, and for envs without closed-loop rollouts."""
         fn = self._ctrl_fn("gp_set_controller")
         if probs is not None and thresholds is not None:
             raise ValueError("set_controller takes probs or thresholds, not both")
@@ -309,7 +316,7 @@ class NativeVecEnv:
         if L != int(A) * M:
             raise _lib.GymPoError(f"set_controller: rows of a {M}-node controller over {int(A)} actions have "
                                   f"{int(A) * M} entries, got {L}")
-        n_space = getattr(getattr(self, "single_observation_space", None), "n", None)
+        n_space = self._controller_n_obs()
         if n_space is not None and n_obs != int(n_space):
             raise _lib.GymPoError(f"set_controller: the table has n_obs = {n_obs}, the env's observation space "
                                   f"{int(n_space)}")
@@ -318,7 +325,8 @@ class NativeVecEnv:
     def rollout_controller(self, K, out=None, store=_CTRL_OUTPUTS):
         """K closed-loop steps in ONE launch: each env's action is drawn on the device by the installed controller
         from the env's current observation and controller node (set_controller). Returns a dict of the outputs
-        named in `store`: obs [K, B] (the env's obs dtype), actions int32 [K, B] (the actions taken), nodes uint8
+        named in `store`: obs [K, B] (the env's obs dtype; uint8 [K, B, n_obs] for a one-hot Taxi), actions int32
+        [K, B] (the actions taken), nodes uint8
         [K, B] (the node each action was chosen in), rew float32 [K, B], term / trunc bool [K, B]. Outputs left out
         of `store` are not written at all (store=() is a pure policy evaluation, read through metrics()). `out`
         may supply preallocated buffers as a dict by name (term / trunc as uint8), checked for shape, dtype, device

@@ -16,6 +16,10 @@ and chained in order, csrc/taxi.hip), so a seeded run reproduces the reference's
 
 Extra keyword arguments beyond the reference: `device`, `rng_mode`, `one_hot` (emit the observation
 index one-hot as uint8 [B, n_obs], a build-side encoding).
+
+Beyond the reference: with `hansen_obs=True` in `rng_mode="philox"` a tabular finite-state controller can be
+installed and run inside the rollout kernel (`set_controller` / `rollout_controller` / `controller_nodes`,
+DESIGN.md 6j), the table indexed by the scalar Hansen obs whether or not the handle emits it one-hot.
 """
 import ctypes
 from functools import partial
@@ -143,6 +147,11 @@ class TaxiVecEnv(NativeVecEnv):
         """Fully reset all environments (extended_taxi.py:232-242). Returns (obs, {})."""
         self.lastaction = None
         return self._reset_impl(seed), {}
+
+    def _controller_n_obs(self):
+        """Closed-loop rollouts (set_controller; hansen_obs=True, rng_mode='philox') index the table by the scalar
+        obs, one-hot handles too, whose Box space has no `.n`."""
+        return self.no
 
     @property
     def reset_distribution(self):

@@ -247,8 +247,9 @@ int gp_plan_run(gp_plan* plan);
 void gp_plan_destroy(gp_plan* plan);
 
 /* ---- closed-loop rollouts: a tabular finite-state controller evaluated inside the rollout kernel ----
- * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), ROCKSAMPLE (either obs), and ANTTAG with the
- * index obs (obs_index = 1) in GP_RNG_PHILOX; every other kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
+ * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), ROCKSAMPLE (either obs), ANTTAG with the
+ * index obs (obs_index = 1) in GP_RNG_PHILOX, and TAXI with the Hansen obs (GP_OBS_HANSEN, one_hot 0 or 1) in
+ * GP_RNG_PHILOX; every other kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
  * one step() per action.)
  *
  * The controller has M = n_nodes nodes (1..8; M = 1 is a memoryless policy obs -> action distribution). With A the
@@ -271,10 +272,20 @@ void gp_plan_destroy(gp_plan* plan);
  * multiply is exact below 64).
  * ANTTAG: the obs is the index obs of the state word; the env draws carry 0x616e7431. A = 5, so L = 5 M <= 40 and rows
  * are padded to 16-B quads as ROCKSAMPLE's are. n_obs is the caller's (the obs space has size^2 * (size^2 + 1) values).
+ * TAXI: obs_kind GP_OBS_HANSEN in GP_RNG_PHILOX, any map and num_passengers; GP_RNG_NUMPY, GP_RNG_REPLAY and the
+ * raw-state obs (GP_OBS_TABLE) are GP_E_UNSUPPORTED, the message saying which applies (the raw-state obs is refused by
+ * decision, not by the kernel: a fully observed Taxi is not pinned by any test yet). The obs is obs_of[s], the scalar
+ * Hansen index of the state the env is in, whether the obs plane is scalar or one-hot (one_hot = 1: gp_rollout_controller
+ * writes obs as uint8 [K,B,n_obs] rows, and the table is still indexed by the scalar). The env draws carry 0x74617869.
+ * A = 5 (the action -1 no-op of gp_step is never emitted), so L = 5 M <= 40; rows hold exactly L entries and are padded
+ * to 16-B quads as ROCKSAMPLE's are, and j is clamped to 5 M - 1, so a padding entry is never chosen. A completed task
+ * whose episode continues (a goal move with num_passengers > 1) does not reset the node. n_obs is the caller's (the
+ * Hansen obs space has 16 * n_locs * (n_locs + 1) values). The table is staged in LDS when the env's tables plus the
+ * table fit the "ctrl_lds_max" budget below (5 x 5 map: M = 1), else read from global memory.
  *
  * gp_set_controller validates the table, uploads it synchronously and zeroes every node; thr_host = NULL removes the
  * controller. The nodes (uint8 [B], handle state) persist across calls; gp_reset zeroes them; gp_step / gp_rollout
- * leave them alone.
+ * (and, TAXI, gp_set_state) leave them alone.
  * gp_rollout_controller runs K steps in one launch. obs [K,B] int32, rew [K,B] float, term / trunc [K,B] uint8 as
  * gp_rollout; actions int32 [K,B]: the actions taken; nodes uint8 [K,B]: the node each action was chosen in. Every
  * output pointer may be NULL (not stored); with all of them NULL the call is a pure policy evaluation, read through
@@ -337,8 +348,9 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * "fused_tiles_per_block", "fused_staged" (1 = LDS-staged outputs + store waves),
  * "fused_tile_envs", "philox_step" (GP_RNG_PHILOX: the counter's step index that the next reset / step draws
  * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
- * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE, ANTTAG: always 0); ROCKSAMPLE
- * and ANTTAG answer the last three too. Unknown keys return
+ * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE, ANTTAG: always 0); ROCKSAMPLE,
+ * ANTTAG and TAXI answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
+ * rollout, 0 = no controller). Unknown keys return
  * GP_E_INVALID. */
 int gp_query(const gp_env* env, const char* key, int64_t* value);
 /* ---- the normal sampler of rng_mode=philox (C-ROOMS noise), diagnostics ----
@@ -388,9 +400,11 @@ int gp_profile_read_resolver(gp_env* env, double* total_ms, int64_t* n_launches)
  *   generic philox rollout even where a compile-time-specialised one exists), "no_wgrid" (GRID numpy mode: 1 =
  *   never the windowed kernel csrc/wgrid.hip), "wg_halo" (its window halo: 256 or 512 draws), "wg_bias" (added
  *   to its predicted reset count: forces window regenerations), "wg_tmode" (its timing-study variants, TM_* in
- *   csrc/wgrid.hip; results invalid for some), "ctrl_lds_max" (GRID closed-loop rollouts, read by
+ *   csrc/wgrid.hip; results invalid for some), "ctrl_lds_max" (GRID and TAXI closed-loop rollouts, read by
  *   gp_set_controller instead: the controller table is staged in LDS when the env's tables plus the table take at
- *   most this many bytes of LDS per block; 0 = always read from global memory, -1 = the default, 32 KB).
+ *   most this many bytes of LDS per block, at most 60 KB; 0 = always read from global memory, -1 = the default,
+ *   32 KB), "persist_bpc" (TAXI / CROOMS / ANTTAG / ROCKSAMPLE persistent rollouts: blocks per CU, 0 = every
+ *   resident block; TAXI keeps the value it was created with for its closed-loop grid too).
  *   gp_debug_reset restores the defaults. Unknown key: GP_E_INVALID. */
 int gp_debug_set(const char* key, int64_t value);
 void gp_debug_reset(void);
