@@ -11,6 +11,10 @@ ones), plus the final internal state and the final PCG64 state of the env's Gene
 
 The `taxi_table` group (TAXI_TABLES, files taxi_table_*.npz, `python tests/golden/make_golden.py taxi_table`) is one
 reference step over every (state, action) row of a Taxi map instead of a trajectory: see run_taxi_table.
+
+The `crooms_table` group (CROOMS_TABLES, files crooms_table_*.npz, `python tests/golden/make_golden.py crooms_table`)
+is one reference step of C-ROOMS over rows aimed at the lines where a step decides something (cell boundaries, the
+goal circle, the clips, the time limit): see run_crooms_table and fixtures.crooms_table_inputs.
 """
 import os
 import sys
@@ -20,6 +24,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+for _p in (os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))):  # tests/ (helpers) and the root (oracle/)
+    if _p not in sys.path:
+        sys.path.insert(1, _p)
 import refload  # noqa: E402
 from fixtures import INDEX, digest, step_actions  # noqa: E402
 
@@ -81,6 +88,15 @@ CASES = {
                                            time_limit=100), 64, 300, 1, 42, True),
     "crooms_card_hansen": (CR, dict(obs_type="hansen", action_type="cardinal", time_limit=100), 64, 300, 2, 43, True),
     "crooms_8_grid": (CR, dict(layout="8", obs_type="grid", action_power=1.5, time_limit=100), 64, 300, 3, 44, True),
+    # cell_size (the reciprocal and the divide paths), goal_threshold and the rewards away from their defaults
+    "crooms_cell2_hansen_rew": (CR, dict(cell_size=2.0, obs_type="hansen", goal_threshold=0.3, step_reward=-0.01,
+                                         wall_reward=-0.5, time_limit=40), 64, 300, 4, 45, True),
+    "crooms_cell15_grid_randgoal": (CR, dict(cell_size=1.5, obs_type="grid", goal_xy=None, wall_reward=-0.5,
+                                             time_limit=40), 64, 300, 5, 46, True),
+    "crooms_cell2_vel_pow2": (CR, dict(cell_size=2.0, obs_type="goal_mdp", goal_xy=None, use_velocity=True,
+                                       action_power=2.0, wall_reward=-0.5, time_limit=40), 64, 300, 6, 47, True),
+    "crooms_cell15_card_vgh8_thr1": (CR, dict(cell_size=1.5, obs_type="vector_goal_hansen8", action_type="cardinal",
+                                              goal_xy=None, goal_threshold=1.0, time_limit=30), 64, 300, 7, 48, True),
 }
 
 
@@ -248,6 +264,86 @@ def run_taxi_table(m, name, spec):
     return meta
 
 
+# ---- C-ROOMS one-step tables: rows aimed at the step's decision lines, stepped once by the reference ----
+# name: (ctor kwargs, seed, rows per family, ring goal (y, x)). action_std = 0 (the action noise is +0.0, so the
+# proposed position is start + action * action_power exactly), dyadic actions, time_limit 3 and rewards that tell goal,
+# wall and step apart. The ring goal is a cell whose eight neighbours are walkable: the fixed goal_xy where the table
+# has one, else written over goal_yx. Row totals are odd and no multiple of 512 (the philox rollout's tile), <= 4096
+# (the one-workgroup exact kernel's limit).
+_CT = dict(action_std=0.0, time_limit=3, step_reward=-0.01, wall_reward=-0.5, goal_reward=2.0)
+_CT_FULL = dict(boundary=1300, ring=2048, time=645)
+_CT_RAND = dict(boundary=1200, ring=2048, goal_wall=150, time=597)
+_CT_THR = dict(ring=2048, time=999)
+CROOMS_TABLES = {
+    "crooms_table_yx_vgmdp": (dict(obs_type="vector_goal_mdp", goal_xy=(4, 4), **_CT), 1, _CT_FULL, (4, 4)),
+    "crooms_table_yx_vmdp_spec": (dict(obs_type="vector_mdp", goal_xy=(12, 4), **_CT), 2, _CT_FULL, (4, 12)),
+    "crooms_table_vel_pow2": (dict(obs_type="vector_goal_mdp", use_velocity=True, action_power=2.0, goal_xy=None,
+                                   **_CT), 3, dict(boundary=1000, ring=2048, clip=300, goal_wall=150, time=597),
+                              (12, 4)),
+    "crooms_table_cell2_hansen": (dict(cell_size=2.0, obs_type="hansen", goal_xy=(5, 5), **_CT), 4, _CT_FULL, (5, 5)),
+    "crooms_table_cell15_grid5": (dict(cell_size=1.5, obs_type="grid", obs_m=5, goal_xy=None, layout="8b", **_CT), 5,
+                                  _CT_RAND, (4, 4)),
+    # cell_size 1.25: floor(x / 1.25) and floor(x * (1 / 1.25)) differ one ulp below the boundaries 3.75, 6.25, 7.5,
+    # 12.5, 13.75 and 15 (1 / 1.25 rounds up); with 1.5 the two agree everywhere (1 / 1.5 rounds down), so only this
+    # table tells the divide from a multiply by the rounded reciprocal
+    "crooms_table_cell125_mdp": (dict(cell_size=1.25, obs_type="mdp", goal_xy=(4, 4), **_CT), 10, _CT_FULL, (4, 4)),
+    "crooms_table_card_goal_mdp": (dict(action_type="cardinal", obs_type="goal_mdp", goal_xy=None, **_CT), 6,
+                                   _CT_RAND, (12, 12)),
+    "crooms_table_thr0": (dict(obs_type="vector_goal_mdp", goal_xy=(5, 5), goal_threshold=0.0, **_CT), 7, _CT_THR,
+                          (5, 5)),
+    "crooms_table_thr1": (dict(obs_type="vector_goal_mdp", goal_xy=(4, 12), goal_threshold=1.0, **_CT), 8, _CT_THR,
+                          (12, 4)),
+    "crooms_table_thr03": (dict(obs_type="vector_goal_mdp", goal_xy=(12, 12), goal_threshold=0.3, **_CT), 9, _CT_THR,
+                           (12, 12)),
+}
+
+
+def run_crooms_table(m, name, spec):
+    """reset(seed), overwrite agent_yx / goal_yx / agent_yx_velocity / elapsed with the table's rows
+    (fixtures.crooms_table_inputs), one step. Recorded: the inputs, the four outputs, the post-step state (the
+    reference's own wall resamples and resets included) and the PCG64 state before and after the step. `oob` and
+    `move` (the effective action * action_power) are the oracle's, which must first reproduce the reference's step
+    bit for bit from the same state: the reference does not expose them."""
+    from crooms_table_oracle import table_oracle_step
+    from fixtures import crooms_table_check_counts, crooms_table_counts, crooms_table_inputs
+    kw, seed, rows, ring_goal = spec
+    meta = dict(kind="crooms_table", kwargs=kw, seed=seed, rows=rows, ring_goal=list(ring_goal),
+                num_envs=sum(rows.values()), numpy=np.__version__, file=f"{name}.npz")
+    B = meta["num_envs"]
+    inp = crooms_table_inputs(meta)
+    env = m["crooms"].CRoomsEnv(B, **kw)
+    env.reset(seed=seed)
+    pre = _rng6(env.rng)
+    goal_in = inp["goal_cell"].astype(np.float64) + 0.5
+    if kw["goal_xy"] is not None:  # a fixed goal stays the reference's own
+        assert np.array_equal(env.goal_yx, goal_in), (env.goal_yx[0], goal_in[0])
+    env.agent_yx, env.goal_yx = inp["agent"].copy(), goal_in.copy()
+    env.agent_yx_velocity, env.elapsed = inp["velocity"].copy(), inp["elapsed"].astype(int)
+    o, r, d, tr, _ = env.step(inp["action"].copy())
+    o = np.asarray(o)
+    gc = np.asarray(env.goal_yx) - 0.5
+    assert r.dtype == np.float32 and np.array_equal(gc, gc.astype(np.int16))
+    arrays = dict(in_family=inp["family"], in_agent=inp["agent"], in_goal_cell=inp["goal_cell"],
+                  in_velocity=inp["velocity"], in_elapsed=inp["elapsed"], in_action=inp["action"],
+                  obs=o.astype(obs_store_dtype(o)), rew=r, term=np.asarray(d, bool), trunc=np.asarray(tr, bool),
+                  agent=np.asarray(env.agent_yx, np.float64), goal_cell=gc.astype(np.int16),
+                  velocity=np.asarray(env.agent_yx_velocity, np.float64), elapsed=env.elapsed.astype(np.int32),
+                  pre_rng_state=pre, rng_state=_rng6(env.rng))
+    ora, out, _ = table_oracle_step(meta, arrays, recording=False)
+    for k, v in dict(obs=out[0], rew=out[1], term=out[2], trunc=out[3], agent=ora.agent, velocity=ora.velocity,
+                     elapsed=ora.elapsed, goal_cell=ora.goal - 0.5).items():
+        assert np.array_equal(np.asarray(v).astype(np.float64), arrays[k].astype(np.float64)), (name, k)
+    assert np.array_equal(_rng6(ora.gen), arrays["rng_state"])
+    arrays["oob"], arrays["move"] = ora.last_oob.astype(bool), ora.last_move
+    meta["counts"] = crooms_table_counts(meta, inp["family"], ora.last_pos, inp["goal_cell"], arrays["oob"],
+                                         arrays["term"], arrays["trunc"], inp["agent"], inp["velocity"], arrays["move"])
+    crooms_table_check_counts(meta, meta["counts"])
+    path = os.path.join(HERE, meta["file"])
+    np.savez_compressed(path, **arrays)
+    assert os.path.getsize(path) <= 256 * 1024, os.path.getsize(path)
+    return meta
+
+
 def main():
     import json
     prefix = sys.argv[1] if len(sys.argv) > 1 else ""
@@ -268,6 +364,12 @@ def main():
         t0 = time.time()
         index.setdefault("taxi_table", {})[name] = run_taxi_table(m, name, spec)
         print(f"{name}: {time.time() - t0:.1f}s {index['taxi_table'][name]['counts']}", flush=True)
+    for name, spec in CROOMS_TABLES.items():
+        if not name.startswith(prefix):
+            continue
+        t0 = time.time()
+        index.setdefault("crooms_table", {})[name] = run_crooms_table(m, name, spec)
+        print(f"{name}: {time.time() - t0:.1f}s {index['crooms_table'][name]['counts']}", flush=True)
     if prefix in ("", "taxi_reset_hist"):
         t0 = time.time()
         index["taxi_reset_hist"] = taxi_reset_histogram(m)

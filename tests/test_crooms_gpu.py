@@ -13,39 +13,14 @@ bit for bit against numpy over numpy's raw words.
 import numpy as np
 import pytest
 
+from crooms_table_oracle import RecordingDraws
 from fixtures import digest, load_case, load_index, step_actions
 from oracle.crooms import CRoomsOracle
-from oracle.draws import NumpyDraws
 
 pytestmark = pytest.mark.gpu
 
 CASES = {k: v for k, v in load_index()["cases"].items() if v["kind"] == "crooms"}
 F32_REL_TOL = 2.0 ** -24  # one float32 rounding of the float64 observation
-
-
-class RecordingDraws(NumpyDraws):
-    """The reference's numpy calls (NumpyDraws) + per-env capture of every value for GPU replay."""
-
-    def __init__(self, gen, B, valid):
-        super().__init__(gen)
-        self.B, self.valid, self.rec = B, valid, {}
-
-    def uniform(self, n):
-        u = super().uniform(n)
-        self.rec["u"] = np.round(u * 2.0 ** 53).astype(np.uint64)  # random() = k * 2^-53 exactly
-        return u
-
-    def choice(self, values, mask, site):
-        v = super().choice(values, mask, site)
-        idx = np.zeros(self.B, np.int32)
-        idx[mask] = np.searchsorted(self.valid, v)
-        self.rec[site] = idx
-        return v
-
-    def record_normal(self, site, mask, v):
-        arr = np.zeros((self.B, 2), np.float64)
-        arr[mask] = v
-        self.rec[site] = arr
 
 
 def make_env(kw, B, **extra):
