@@ -459,6 +459,17 @@ int gp_controller_nodes(gp_env* env, uint8_t* get, const uint8_t* set, void* str
   return env->be->controller_nodes(get, set, (hipStream_t)stream);
 }
 
+int gp_set_controller_population(gp_env* env, int n_ctrl, int64_t group_envs, int n_nodes, int n_obs, float gamma,
+                                 const uint32_t* thr_host) {
+  GP_REQUIRE_ENV();
+  return env->be->set_controller_population(n_ctrl, group_envs, n_nodes, n_obs, gamma, thr_host);
+}
+
+int gp_controller_scores(gp_env* env, double* out, int cap_rows, int clear) {
+  GP_REQUIRE_ENV();
+  return env->be->controller_scores(out, cap_rows, clear);
+}
+
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream) {
   GP_REQUIRE_ENV();
   return env->be->get_state(a, b, c, d, (hipStream_t)stream);

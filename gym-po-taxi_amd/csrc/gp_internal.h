@@ -116,6 +116,16 @@ struct EnvBackend {
     gp_set_error("controllers are not supported by this env kind");
     return GP_E_UNSUPPORTED;
   }
+  // Controller populations (gp_set_controller_population / gp_controller_scores): GRID only.
+  virtual int set_controller_population(int n_ctrl, int64_t group_envs, int n_nodes, int n_obs, float gamma,
+                                        const uint32_t* thr_host) {
+    gp_set_error("controller populations are not supported by this env kind (GRID only)");
+    return GP_E_UNSUPPORTED;
+  }
+  virtual int controller_scores(double* out, int cap_rows, int clear) {
+    gp_set_error("controller populations are not supported by this env kind (GRID only)");
+    return GP_E_UNSUPPORTED;
+  }
   virtual int valid_cells(int which, int32_t* out, int cap) const { return 0; }
   virtual int metrics(double out[4]) = 0;
   // Syncs and reports device-side failures of earlier launches (GP_E_DEVICE); kinds without

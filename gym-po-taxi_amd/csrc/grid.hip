@@ -2646,8 +2646,15 @@ __global__ __launch_bounds__(TPB) void grid_rollout_counter(GridDev p, int K, ui
           philox_draws(p, env, step0 + k, k53, gi, ai);
         }
       }
-      counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], a4[i], k53, gi, ai, r[i], tm[i], tr[i], rsum, eps, lens);
-      nst += env < p.B;
+      float r1 = 0.f;  // the step's own contributions: the padding lanes of a ragged last block (env >= B) never
+      uint32_t e1 = 0, l1 = 0;  // enter the metrics, as in grid_step_numpy
+      counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], a4[i], k53, gi, ai, r[i], tm[i], tr[i], r1, e1, l1);
+      if (env < p.B) {
+        rsum += r1;
+        eps += e1;
+        lens += l1;
+        nst += 1;
+      }
     }
     store4<float>(rew + off, env0, p.B, r);
     store4<uint8_t>(term + off, env0, p.B, tm);
@@ -2745,10 +2752,17 @@ __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDe
       const uint32_t a = (j * c.inv_m) >> 16;  // j / M
       n4[i] = nd[i];
       a4[i] = (int32_t)a;
-      counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], (int)a, k53, gi, ai, r[i], tm[i], tr[i], rsum, eps, lens);
+      float r1 = 0.f;  // (the padding lanes of a ragged last block never enter the metrics: grid_rollout_counter)
+      uint32_t e1 = 0, l1 = 0;
+      counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], (int)a, k53, gi, ai, r[i], tm[i], tr[i], r1, e1, l1);
       nd[i] = (tm[i] | tr[i]) ? (uint8_t)0 : (uint8_t)(j - a * (uint32_t)c.M);  // j % M; episode end: node 0
       ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
-      nst += env < p.B;
+      if (env < p.B) {
+        rsum += r1;
+        eps += e1;
+        lens += l1;
+        nst += 1;
+      }
     }
     if (act) store4<int32_t>(act + off, env0, p.B, a4);
     if (nodes) store4<uint8_t>(nodes + off, env0, p.B, n4);
@@ -2766,6 +2780,165 @@ __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDe
   }
   store4<uint8_t>(c.node, env0, p.B, nd);
   add_metrics(p, rsum, eps, lens, nst);
+}
+
+// ------------------------------------------------------------------ closed-loop rollout: populations ----
+// grid_rollout_controller for P controllers side by side with one score row per controller
+// (gp_set_controller_population / gp_controller_scores; semantics in include/gym_po_amd.h). Env e is driven by
+// controller e / G, G a multiple of EPB, so every block serves exactly one controller: it offsets the table pointer
+// once, stages (CL) only its own controller's table behind the env's tables, and owns one score slot, as it owns its
+// MetricSlot. Per env-step beside the sibling's work: one float multiply for the discounted term, one for the weight,
+// and two double adds. Envs past B in the ragged last block never enter the scores.
+struct PopSlot {  // one block's scores, summed per group in block order by gp_controller_scores
+  double return_sum, disc_sum;
+  unsigned long long episodes, length_sum, env_steps;
+  unsigned long long pad[3];
+};
+struct PopDev {
+  CtrlDev c;       // thr: [P][M][n_obs][L]; bytes: ONE controller's table; node, lds_off as for one controller
+  int32_t bpg;     // blocks per group, G / EPB
+  const float* W;  // [65536] discount weight by elapsed count: W[0] = 1, W[t] = fl32(W[t-1] * gamma)
+  PopSlot* slots;  // [nblk]
+};
+
+// Per-block scores into the block's own slot: per-thread double sums, reduced in double (wave shuffles, then the
+// waves' partials in thread order), plain += (no other block touches the slot; launches on a stream are ordered).
+__device__ void add_scores(const PopDev& q, double rs, double ds, uint32_t eps, uint32_t lens, uint32_t nsteps) {
+  __shared__ double s_r[TPB / 64], s_d[TPB / 64];
+  __shared__ uint32_t s_e[TPB / 64], s_l[TPB / 64], s_n[TPB / 64];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    rs += __shfl_xor(rs, d, 64);
+    ds += __shfl_xor(ds, d, 64);
+    eps += __shfl_xor(eps, d, 64);
+    lens += __shfl_xor(lens, d, 64);
+    nsteps += __shfl_xor(nsteps, d, 64);
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) { s_r[wid] = rs; s_d[wid] = ds; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nsteps; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = 0, dd = 0; uint32_t e = 0, l = 0, n = 0;
+    for (int w = 0; w < TPB / 64; ++w) { r += s_r[w]; dd += s_d[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
+    PopSlot& m = q.slots[blockIdx.x];
+    m.return_sum += r;
+    m.disc_sum += dd;
+    m.episodes += e;
+    m.length_sum += l;
+    m.env_steps += n;
+  }
+}
+
+template <int OK, bool LT = false, bool CL = false>
+__global__ __launch_bounds__(TPB) void grid_rollout_population(GridDev p, PopDev q, int K, uint64_t step0,
+                                                               int32_t* __restrict__ obs, int32_t* __restrict__ act,
+                                                               uint8_t* __restrict__ nodes, float* __restrict__ rew,
+                                                               uint8_t* __restrict__ term,
+                                                               uint8_t* __restrict__ trunc) {
+  static_assert(OK == GP_OBS_HANSEN || OK == GP_OBS_TABLE, "the controller conditions on a scalar obs");
+  const CtrlDev& c = q.c;
+  __shared__ uint64_t s_thr[64];
+  extern __shared__ __attribute__((aligned(16))) char dyn[];
+  // this block's controller: the tables are [M][n_obs][L] each, back to back (16-B multiples: L % 4 == 0)
+  const uint32_t* gthr =
+      c.thr + (size_t)((int)blockIdx.x / q.bpg) * ((size_t)c.M * (size_t)c.n_obs * (size_t)c.L);
+  if (threadIdx.x < p.nact * p.nact) s_thr[threadIdx.x] = p.thr[threadIdx.x];
+  if constexpr (LT) lds_image_copy(dyn, p.limg, p.lds.jt.off);  // all but the PCG jump tables (last)
+  if constexpr (CL) lds_image_copy(dyn + c.lds_off, reinterpret_cast<const char*>(gthr), c.bytes);
+  __syncthreads();
+  const uint32_t* cthr = CL ? reinterpret_cast<const uint32_t*>(dyn + c.lds_off) : gthr;
+  const auto tb = make_tabs<LT>(p, dyn);
+  const int env0 = blockIdx.x * EPB + threadIdx.x * EPT;
+  uint32_t ae4[4];
+  load4<uint32_t>(p.ae, env0, p.B, ae4);
+  int g4[4];
+  if (p.fixed_goal < 0) {
+    uint16_t gg[4];
+    load4<uint16_t>(p.goal, env0, p.B, gg);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g4[i] = gg[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g4[i] = p.fixed_goal;
+  }
+  uint8_t nd[4];
+  load4<uint8_t>(c.node, env0, p.B, nd);
+  int32_t ob[4];  // the obs of the state each env is in (what the previous step, or the reset, emitted)
+  float w4[4];    // the env's discount weight before its next step: gamma^elapsed by sequential float products
+  const float gamma = q.W[1];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
+      if (env0 + i < p.B) atomicOr(&p.ctl->err, GP_DERR_CTRL);
+      nd[i] = (uint8_t)(c.M - 1);
+    }
+    ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
+    w4[i] = q.W[ae4[i] >> 16];  // (elapsed is 16 bits: inside the 65,536-entry table)
+  }
+  float rsum = 0.f;
+  uint32_t eps = 0, lens = 0, nst = 0;
+  double grs = 0., gds = 0.;  // this thread's share of its group's return and discounted return
+  for (int k = 0; k < K; ++k) {
+    const size_t off = (size_t)k * p.B;
+    const uint64_t step = step0 + k;
+    int32_t a4[4];
+    uint8_t n4[4];
+    float r[4];
+    uint8_t tm[4], tr[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int env = env0 + i;
+      const bool live = env < p.B;
+      uint64_t k53 = 0;
+      uint32_t gi = 0, ai = 0, y = 0;
+      if (live) {
+        philox_draws(p, env, step, k53, gi, ai);
+        y = philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG, p.key0, p.key1).x[0] >> 1;
+      }
+      uint32_t o = (uint32_t)ob[i];
+      if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
+        if (live) atomicOr(&p.ctl->err, GP_DERR_CTRL);
+        o = (uint32_t)c.n_obs - 1u;
+      }
+      const uint32_t* row = cthr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
+      const uint32_t j = min(ctrl_search(row, c.L, y), (uint32_t)c.L - 1u);
+      const uint32_t a = (j * c.inv_m) >> 16;  // j / M
+      n4[i] = nd[i];
+      a4[i] = (int32_t)a;
+      float r1 = 0.f;  // (the padding lanes of a ragged last block enter neither the metrics nor the scores)
+      uint32_t e1 = 0, l1 = 0;
+      counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], (int)a, k53, gi, ai, r[i], tm[i], tr[i], r1, e1, l1);
+      const bool ended = (tm[i] | tr[i]) != 0;
+      const float dterm = __fmul_rn(w4[i], r[i]);  // one rounding, never contracted with the add below
+      if (live) {
+        rsum += r1;
+        eps += e1;
+        lens += l1;
+        nst += 1;
+        grs += (double)r[i];
+        gds += (double)dterm;
+      }
+      w4[i] = ended ? 1.0f : __fmul_rn(w4[i], gamma);
+      nd[i] = ended ? (uint8_t)0 : (uint8_t)(j - a * (uint32_t)c.M);  // j % M; episode end: node 0
+      ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
+    }
+    if (act) store4<int32_t>(act + off, env0, p.B, a4);
+    if (nodes) store4<uint8_t>(nodes + off, env0, p.B, n4);
+    if (rew) store4<float>(rew + off, env0, p.B, r);
+    if (term) store4<uint8_t>(term + off, env0, p.B, tm);
+    if (trunc) store4<uint8_t>(trunc + off, env0, p.B, tr);
+    if (obs) store4<int32_t>(obs + off, env0, p.B, ob);
+  }
+  store4<uint32_t>(p.ae, env0, p.B, ae4);
+  if (p.fixed_goal < 0) {
+    uint16_t gg[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) gg[i] = (uint16_t)g4[i];
+    store4<uint16_t>(p.goal, env0, p.B, gg);
+  }
+  store4<uint8_t>(c.node, env0, p.B, nd);
+  add_metrics(p, rsum, eps, lens, nst);
+  add_scores(q, grs, gds, eps, lens, nst);  // the block's counts are its group's share
 }
 
 // Philox / replay reset: every env draws goal then agent from its own counter.
@@ -2878,6 +3051,9 @@ struct GridBackend : EnvBackend {
     else if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
     else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
     else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
+    else if (!strcmp(key, "controller_population")) *v = pop_P;  // controllers of the installed population (0 = none)
+    else if (!strcmp(key, "controller_group_envs")) *v = pop_G;
+    else if (!strcmp(key, "controller_group_multiple")) *v = EPB;  // group_envs must be a multiple of this
     else return EnvBackend::query(key, v);
     return GP_OK;
   }
@@ -2922,6 +3098,22 @@ struct GridBackend : EnvBackend {
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override;
   int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override;
+  // controller populations (grid_rollout_population): `ctrl` then describes ONE controller of the population (its M,
+  // n_obs, L, per-controller bytes and staging decision; thr the base of all P tables), so that the nodes, the
+  // queries and gp_reset see "a controller is installed"; pop_P > 0 says it is a population
+  int pop_P = 0;             // controllers (0: no population installed)
+  int64_t pop_G = 0;         // envs per group
+  int pop_bpg = 1;           // blocks per group: pop_G / EPB, at most nblk (one group however large G is)
+  DevBuf b_pw, b_pslot;      // the weight table W [65536] and the per-block score slots [nblk]
+  void drop_population() {  // (after a device sync: no launch reads W or the slots any more)
+    pop_P = 0;
+    pop_G = 0;
+    (void)b_pw.alloc(0);
+    (void)b_pslot.alloc(0);
+  }
+  int set_controller_population(int n_ctrl, int64_t group_envs, int n_nodes, int n_obs, float gamma,
+                                const uint32_t* thr_host) override;
+  int controller_scores(double* out, int cap_rows, int clear) override;
 #ifdef GP_STAMPS
   int debug_stamps(unsigned long long* out, int cap) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
@@ -3323,6 +3515,7 @@ static int dispatch_obs(int ok, F&& f) {
 int GridBackend::reset(void* obs, hipStream_t s) {
   GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * nslots, s));
   if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
+  if (pop_P) GP_HIP_CHECK(hipMemsetAsync(b_pslot.p, 0, sizeof(PopSlot) * (size_t)d.nblk, s));  // and every score
   const unsigned g1 = (unsigned)((B + TPB - 1) / TPB);
   const bool rgoal = d.fixed_goal < 0, ragent = d.fixed_agent < 0;
   const unsigned gp = (unsigned)grid_persist;
@@ -3563,6 +3756,7 @@ int GridBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host
   GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
   if (!thr_host) {
     ctrl = CtrlDev{};
+    drop_population();
     int e;
     if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
     return GP_OK;
@@ -3579,6 +3773,7 @@ int GridBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host
   }
   if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L)) return e;
   ctrl = CtrlDev{};  // (no controller if an allocation below fails)
+  drop_population();  // a single controller replaces a population
   int e;
   if ((e = b_cthr.alloc(n * sizeof(uint32_t))) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
   GP_HIP_CHECK(hipMemcpy(b_cthr.p, thr_host, n * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -3609,7 +3804,19 @@ int GridBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* nod
     constexpr int OK = decltype(okc)::value;
     if constexpr (OK == GP_OBS_HANSEN || OK == GP_OBS_TABLE) {
       timer.begin(s);
-      if (ctrl.lds_off >= 0)  // the controller table staged behind the env's tables (set_controller decided)
+      if (pop_P) {  // a population: the same three table placements, per controller
+        const PopDev q{ctrl, pop_bpg, b_pw.as<float>(), b_pslot.as<PopSlot>()};
+        if (ctrl.lds_off >= 0)
+          hipLaunchKernelGGL((grid_rollout_population<OK, true, true>), dim3(d.nblk), dim3(TPB),
+                             (size_t)ctrl.lds_off + (size_t)ctrl.bytes, s, d, q, K, philox_step, (int32_t*)obs, act,
+                             nodes, rew, term, trunc);
+        else if (d.lds.total > 0)
+          hipLaunchKernelGGL((grid_rollout_population<OK, true>), dim3(d.nblk), dim3(TPB), (size_t)d.lds.jt.off, s, d,
+                             q, K, philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+        else
+          hipLaunchKernelGGL((grid_rollout_population<OK, false>), dim3(d.nblk), dim3(TPB), 0, s, d, q, K,
+                             philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+      } else if (ctrl.lds_off >= 0)  // the controller table staged behind the env's tables (set_controller decided)
         hipLaunchKernelGGL((grid_rollout_controller<OK, true, true>), dim3(d.nblk), dim3(TPB),
                            (size_t)ctrl.lds_off + (size_t)ctrl.bytes, s, d, ctrl, K, philox_step, (int32_t*)obs, act,
                            nodes, rew, term, trunc);
@@ -3637,6 +3844,104 @@ int GridBackend::controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t 
   }
   if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
   if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
+  return GP_OK;
+}
+
+// ---- controller populations ----
+int GridBackend::set_controller_population(int n_ctrl, int64_t group_envs, int n_nodes, int n_obs, float gamma,
+                                           const uint32_t* thr_host) {
+  if (int e = controller_unsupported("gp_set_controller_population")) return e;
+  if (!thr_host) return set_controller(0, 0, nullptr);  // removes whichever is installed
+  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the tables being replaced)
+  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
+    gp_set_error("gp_set_controller_population: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)",
+                 n_nodes, n_obs);
+    return GP_E_INVALID;
+  }
+  if (group_envs < EPB || group_envs % EPB) {
+    gp_set_error("gp_set_controller_population: group_envs must be a positive multiple of %d, the envs of one rollout "
+                 "block (got %lld)", EPB, (long long)group_envs);
+    return GP_E_INVALID;
+  }
+  const int64_t groups = (B + group_envs - 1) / group_envs;
+  if (n_ctrl < 1 || (int64_t)n_ctrl != groups) {
+    gp_set_error("gp_set_controller_population: %lld envs in groups of %lld make %lld groups, not n_ctrl = %d",
+                 (long long)B, (long long)group_envs, (long long)groups, n_ctrl);
+    return GP_E_INVALID;
+  }
+  if (!(gamma > 0.f && gamma <= 1.f)) {  // (NaN fails both comparisons)
+    gp_set_error("gp_set_controller_population: gamma must be in (0, 1] (got %g)", (double)gamma);
+    return GP_E_INVALID;
+  }
+  const int L = d.nact * n_nodes;
+  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n1 = rows * (size_t)L, n = n1 * (size_t)n_ctrl;
+  if (n > ((size_t)1 << 28)) {
+    gp_set_error("gp_set_controller_population: tables of %zu entries in total are too large (max 2^28)", n);
+    return GP_E_INVALID;
+  }
+  for (int c = 0; c < n_ctrl; ++c)
+    if (int e = ctrl_validate_rows(thr_host + (size_t)c * n1, rows, n_obs, L)) {
+      const std::string row_error = gp_last_error();  // names the node and obs
+      gp_set_error("gp_set_controller_population: controller %d: %s", c, row_error.c_str());
+      return e;
+    }
+  std::vector<float> W(65536);
+  float w = 1.0f;
+  for (float& x : W) {  // sequential float32 products, one rounding each (a product alone cannot contract)
+    x = w;
+    w = w * gamma;
+  }
+  ctrl = CtrlDev{};  // (nothing installed if an allocation below fails)
+  drop_population();
+  int e;
+  if ((e = b_cthr.alloc(n * sizeof(uint32_t))) || (e = b_cnode.alloc((size_t)B + 16)) ||  // nodes zeroed
+      (e = b_pw.upload(W)) || (e = b_pslot.alloc(sizeof(PopSlot) * (size_t)d.nblk)))      // scores zeroed
+    return e;
+  GP_HIP_CHECK(hipMemcpy(b_cthr.p, thr_host, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  ctrl.thr = b_cthr.as<uint32_t>();
+  ctrl.node = b_cnode.as<uint8_t>();
+  ctrl.M = n_nodes;
+  ctrl.n_obs = n_obs;
+  ctrl.L = L;
+  ctrl.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
+  ctrl.bytes = (int32_t)std::min(n1 * sizeof(uint32_t), (size_t)INT32_MAX);
+  // the staging rule of set_controller on ONE controller's table: a block stages only its own
+  const int knob = gp_debug_knobs().ctrl_lds_max;
+  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
+  ctrl.lds_off = (d.lds.total > 0 && (size_t)d.lds.jt.off + n1 * sizeof(uint32_t) <= budget) ? d.lds.jt.off : -1;
+  pop_P = n_ctrl;
+  pop_G = group_envs;
+  pop_bpg = (int)std::min<int64_t>(group_envs / EPB, d.nblk);
+  return GP_OK;
+}
+
+int GridBackend::controller_scores(double* out, int cap_rows, int clear) {
+  if (int e = controller_unsupported("gp_controller_scores")) return e;
+  if (!pop_P) {
+    gp_set_error("gp_controller_scores without a population (gp_set_controller_population)");
+    return GP_E_STATE;
+  }
+  if (!out || cap_rows < pop_P) {
+    gp_set_error("gp_controller_scores: out must hold %d rows of 5 (cap_rows = %d)", pop_P, cap_rows);
+    return GP_E_INVALID;
+  }
+  if (int e = check()) return e;  // syncs; the device-error check of gp_metrics
+  std::vector<PopSlot> m((size_t)d.nblk);
+  GP_HIP_CHECK(hipMemcpy(m.data(), b_pslot.p, sizeof(PopSlot) * m.size(), hipMemcpyDeviceToHost));
+  const int bpg = pop_bpg;
+  for (int c = 0; c < pop_P; ++c) {
+    double* o = out + 5 * (size_t)c;
+    double eps = 0, rs = 0, ls = 0, ns = 0, ds = 0;
+    for (int b = c * bpg; b < std::min((c + 1) * bpg, (int)d.nblk); ++b) {  // the group's blocks, in block order
+      eps += (double)m[b].episodes;
+      rs += m[b].return_sum;
+      ls += (double)m[b].length_sum;
+      ns += (double)m[b].env_steps;
+      ds += m[b].disc_sum;
+    }
+    o[0] = eps; o[1] = rs; o[2] = ls; o[3] = ns; o[4] = ds;
+  }
+  if (clear) GP_HIP_CHECK(hipMemset(b_pslot.p, 0, sizeof(PopSlot) * m.size()));
   return GP_OK;
 }
 

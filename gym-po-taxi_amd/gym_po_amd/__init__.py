@@ -14,7 +14,7 @@ device memory.
 from .envs import *  # noqa: E402,F401,F403
 from .envs import __all__ as _envs_all  # noqa: E402
 
-from .controller import controller_thresholds  # noqa: E402
+from .controller import controller_thresholds, population_thresholds  # noqa: E402
 
-__all__ = list(_envs_all) + ["controller_thresholds"]
+__all__ = list(_envs_all) + ["controller_thresholds", "population_thresholds"]
 __version__ = "0.1.0"

@@ -97,6 +97,9 @@ SIGNATURES = {
     "gp_set_controller": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "gp_rollout_controller": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_controller_nodes": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "gp_set_controller_population": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_float, _vp]),
+    "gp_controller_scores": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int]),
     "gp_get_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_replay": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

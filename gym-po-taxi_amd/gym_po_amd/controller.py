@@ -43,3 +43,19 @@ def controller_thresholds(probs):
     last = (L - 1) - np.argmax(rows[..., ::-1] > 0, axis=-1)  # the last nonzero entry of each row
     t[np.arange(L) >= last[..., None]] = TOP
     return t.astype(np.uint32)
+
+
+def population_thresholds(probs):
+    """float probs [P, M, n_obs, A, M], P controllers of one shape -> uint32 thresholds [P, M, n_obs, A * M] for
+    `NativeVecEnv.set_controller_population`: `controller_thresholds` applied to each controller. Raises ValueError
+    as it does, the message naming the controller first."""
+    p = np.asarray(probs, dtype=np.float64)
+    if p.ndim != 5 or p.shape[0] < 1:
+        raise ValueError(f"probs must be [P, M, n_obs, A, M] with P >= 1, got shape {np.shape(probs)}")
+    out = []
+    for c in range(p.shape[0]):
+        try:
+            out.append(controller_thresholds(p[c]))
+        except ValueError as e:
+            raise ValueError(f"controller {c}: {e}") from None
+    return np.stack(out)

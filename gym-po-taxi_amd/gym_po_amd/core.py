@@ -322,6 +322,72 @@ class NativeVecEnv:
                                   f"{int(n_space)}")
         check(fn(self._handle, M, n_obs, ctypes.c_void_p(t.ctypes.data)), "gp_set_controller")
 
+    _SCORE_FIELDS = ("episodes", "return_sum", "length_sum", "env_steps", "discounted_return_sum")
+
+    def set_controller_population(self, probs=None, thresholds=None, group_envs=None, gamma=1.0):
+        """Install P controllers side by side (FourRooms / ROOMS with a scalar obs in rng_mode='philox'), or remove
+        whatever controller is installed when `probs` and `thresholds` are both None. Env e is driven by controller
+        e // group_envs; `controller_scores()` then gives one score row per controller, its discounted return under
+        `gamma` (float32, in (0, 1]) included. `probs`: float [P, M, n_obs, A, M], lowered by
+        `controller.population_thresholds`; `thresholds`: that uint32 [P, M, n_obs, A * M] table itself.
+        `group_envs` must be a multiple of query('controller_group_multiple') (1024) that splits the envs into exactly
+        P groups, the last one possibly short; None takes ceil(num_envs / P) rounded up to such a multiple and raises
+        GymPoError if that does not give P groups. Replaces a controller installed by set_controller (and is replaced
+        by it); every node and score becomes 0. rollout_controller() runs it like a single controller."""
+        fn = self._ctrl_fn("gp_set_controller_population")
+        if probs is not None and thresholds is not None:
+            raise ValueError("set_controller_population takes probs or thresholds, not both")
+        if probs is None and thresholds is None:
+            check(fn(self._handle, 0, 0, 0, 0, 1.0, None), "gp_set_controller_population")
+            return
+        if probs is not None:
+            from .controller import population_thresholds
+            thresholds = population_thresholds(probs)
+        t = np.ascontiguousarray(thresholds)
+        if t.dtype != np.uint32 or t.ndim != 4 or t.shape[0] < 1:
+            raise ValueError(f"thresholds must be a uint32 array [P, M, n_obs, A * M], got {t.dtype} {t.shape}")
+        P, M, n_obs, L = t.shape
+        A = getattr(getattr(self, "single_action_space", None), "n", None)
+        if A is None or self._action_dtype != "int32":
+            raise _lib.GymPoError("set_controller_population: the env has no discrete action space")
+        if L != int(A) * M:
+            raise _lib.GymPoError(f"set_controller_population: rows of a {M}-node controller over {int(A)} actions "
+                                  f"have {int(A) * M} entries, got {L}")
+        n_space = self._controller_n_obs()
+        if n_space is not None and n_obs != int(n_space):
+            raise _lib.GymPoError(f"set_controller_population: the tables have n_obs = {n_obs}, the env's observation "
+                                  f"space {int(n_space)}")
+        if group_envs is None:
+            mult = 1024  # gp_query "controller_group_multiple" (asked below where the handle answers it)
+            try:
+                mult = self.query("controller_group_multiple")
+            except _lib.GymPoError:
+                pass  # another env kind: the call below says that populations are unsupported there
+            per_group = -(-self.num_envs // P)  # ceil
+            group_envs = -(-per_group // mult) * mult
+            if -(-self.num_envs // group_envs) != P:
+                raise _lib.GymPoError(f"set_controller_population: {self.num_envs} envs in groups of {group_envs} (the "
+                                      f"next multiple of {mult}) do not make {P} groups; pass group_envs")
+        check(fn(self._handle, P, int(group_envs), M, n_obs, float(gamma), ctypes.c_void_p(t.ctypes.data)),
+              "gp_set_controller_population")
+
+    def controller_scores(self, clear=False):
+        """The per-controller scores of the installed population since reset() / the last clear (syncs): a dict of
+        numpy arrays [P]: episodes, length_sum, env_steps (int64), return_sum and discounted_return_sum (float64).
+        clear=True zeroes them after reading. Raises GymPoError without a population, or if a device-side failure
+        invalidated the run (see check())."""
+        fn = self._ctrl_fn("gp_controller_scores")
+        try:
+            P = self.query("controller_population")
+        except _lib.GymPoError:
+            P = 0  # another env kind: the call below says that populations are unsupported there
+        buf = (ctypes.c_double * (5 * max(P, 1)))()
+        check(fn(self._handle, buf, max(P, 1), int(bool(clear))), "gp_controller_scores")
+        a = np.array(buf[:5 * P], dtype=np.float64).reshape(P, 5)
+        sums = ("return_sum", "discounted_return_sum")  # float64; the three counts are exact integers
+        return {name: (a[:, i].copy() if name in sums else a[:, i].astype(np.int64))
+                for i, name in enumerate(self._SCORE_FIELDS)}
+
     def rollout_controller(self, K, out=None, store=_CTRL_OUTPUTS):
         """K closed-loop steps in ONE launch: each env's action is drawn on the device by the installed controller
         from the env's current observation and controller node (set_controller). Returns a dict of the outputs

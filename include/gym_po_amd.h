@@ -298,6 +298,49 @@ int gp_rollout_controller(gp_env* env, int K, void* obs, int32_t* actions, uint8
                           uint8_t* trunc, void* stream);
 int gp_controller_nodes(gp_env* env, uint8_t* get, const uint8_t* set, void* stream);
 
+/* ---- controller populations: P controllers run side by side, one score row per controller ----
+ * GRID only, under the kind and mode gate of gp_set_controller (GP_RNG_PHILOX, GP_OBS_HANSEN / GP_OBS_TABLE); every
+ * other kind: GP_E_UNSUPPORTED. (No reference counterpart.)
+ *
+ * Groups. A population is P = n_ctrl controllers that share n_nodes M, n_obs and the env's action count A. Env e is
+ * driven by controller p = e / G, G = group_envs a positive multiple of 1024 (the envs of one rollout block, gp_query
+ * "controller_group_multiple"), so that every block serves exactly one controller. P must equal ceil(B / G); the last
+ * group is short when B is no multiple of G. thr_host is uint32 [P][M][n_obs][L], L = A * M: P tables of
+ * gp_set_controller, back to back.
+ *
+ * Choice rule. Exactly the single-controller rule above with thr[p] in place of thr: the 0x67706f63 Philox block of
+ * (env, step), y = x0 >> 1, j = #{i < L : y >= thr[p][node][obs][i]}, action = j / M, node = j % M or 0 at episode
+ * end, the obs / node clamps and GP_DERR_CTRL. The draws are keyed by (env, step), so the trajectory of env e under a
+ * population equals its trajectory on a same-seed twin handle with thr[e / G] installed by gp_set_controller.
+ *
+ * Scores. Each controller has five counters, accumulated by every closed-loop launch since they were last zeroed, in
+ * this order: episodes, return_sum, length_sum, env_steps, discounted_return_sum. The first four mean for the group
+ * what gp_metrics means for the batch: the rewards of all its env-steps, the lengths of the episodes that ended.
+ * discounted_return_sum = sum of fl32(w * rew) over the group's env-steps, w the env's discount weight before the
+ * step: at launch start w = W[elapsed] from the env's stored elapsed count; after each step w = 1.0f if the step ended
+ * the episode, else fl32(w * gamma). W is a float32 table of 65,536 entries built on the host, W[0] = 1,
+ * W[t] = fl32(W[t-1] * gamma), gamma a float32 in (0, 1]. Every product is rounded once (never contracted into an
+ * FMA), so a launch that begins mid-episode, or after gp_set_state, weighs as one long launch would, with no per-env
+ * state beyond the elapsed count. Each thread adds its float terms (return_sum: the float rewards) into doubles;
+ * they are reduced per block in double and added into a slot only that block writes (no float or double atomics);
+ * the host sums a group's slots in block order. Results are deterministic for a given B, G and launch sequence.
+ * gp_metrics keeps its meaning and its bits: a population run reports what a twin running the same actions reports.
+ *
+ * gp_set_controller_population validates every row as gp_set_controller does (the message names the controller, the
+ * node and the obs), uploads synchronously, zeroes every node and score, and replaces any installed controller or
+ * population; thr_host = NULL removes whichever is installed. GP_E_INVALID: group_envs no positive multiple of 1024;
+ * n_ctrl != ceil(B / group_envs); gamma outside (0, 1] or NaN; n_nodes outside [1, 8] or n_obs outside [1, 2^24];
+ * more than 2^28 table entries in total; a bad row. gp_set_controller in turn removes a population. gp_reset zeroes
+ * the scores together with the nodes. gp_rollout_controller runs whichever is installed; gp_controller_nodes is
+ * unchanged. A block stages only its own controller's table in LDS, under gp_set_controller's budget rule applied to
+ * one controller's bytes ("ctrl_lds_max" included).
+ * gp_controller_scores: out (host, [P][5] doubles in the order above; cap_rows >= P rows, else GP_E_INVALID); syncs
+ * and runs the device-error check of gp_metrics; clear != 0 zeroes the scores after reading. GP_E_STATE without a
+ * population. */
+int gp_set_controller_population(gp_env* env, int n_ctrl, int64_t group_envs, int n_nodes, int n_obs, float gamma,
+                                 const uint32_t* thr_host);
+int gp_controller_scores(gp_env* env, double* out, int cap_rows, int clear);
+
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
@@ -350,7 +393,9 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
  * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE, ANTTAG: always 0); ROCKSAMPLE,
  * ANTTAG and TAXI answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
- * rollout, 0 = no controller). Unknown keys return
+ * rollout, 0 = no controller). GRID also: "controller_population" (P of the installed population, 0 = none),
+ * "controller_group_envs" (its G), "controller_group_multiple" (1024: what G must be a multiple of); with a population
+ * "controller_nodes" and "controller_lds" answer for one controller's table. Unknown keys return
  * GP_E_INVALID. */
 int gp_query(const gp_env* env, const char* key, int64_t* value);
 /* ---- the normal sampler of rng_mode=philox (C-ROOMS noise), diagnostics ----
