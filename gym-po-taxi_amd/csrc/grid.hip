@@ -702,7 +702,9 @@ __global__ __launch_bounds__(TPB) void grid_step_numpy(GridDev p, const int32_t*
 // Fast path: the j-th resetter of a call takes word (call base + j). Every block checks its own
 // words for Lemire rejections and publishes a flag; a block whose range or any predecessor's
 // range holds a rejection recomputes exact positions by walking the stream (rare: p ~ 1e-8
-// per word). The last block publishes the next RNG state (it waited on every other block).
+// per word). With two calls a rejected goal word of ANY block moves the base of every block's
+// agent words, so there every block waits for every flag. The last block publishes the next
+// RNG state (it waited on every other block).
 #define RM_RESET 1  // every env resets (reset()); U0 = 0, no random(B) before the words
 
 template <int OK>
@@ -763,9 +765,11 @@ __global__ __launch_bounds__(TPB) void grid_resolve_numpy(GridDev p, void* __res
   const uint32_t myrej = __syncthreads_or((int)rj) ? 1u : 0u;
   if (threadIdx.x == 0 && (int)blockIdx.x != p.fault_block)
     st_flag32(&p.rflag[blockIdx.x], ((epoch + 1u) << 1) | myrej);
-  // wait for every predecessor block's flag (all K2 blocks are resident: gridDim <= 256)
+  // wait for every predecessor block's flag, with two calls for every block's (all K2 blocks are resident,
+  // gridDim <= 256, and each has published its own flag above)
   uint32_t prej = 0;
-  for (int j = threadIdx.x; j < (int)blockIdx.x; j += TPB) {
+  const int nwait = ncalls == 2 ? (int)gridDim.x : (int)blockIdx.x;
+  for (int j = threadIdx.x; j < nwait; j += TPB) {
     uint32_t f = ld_flag(&p.rflag[j]);
     uint32_t spins = 0;
     while ((f >> 1) != epoch + 1u) {

@@ -263,7 +263,8 @@ class FourRoomsOracle(_GridOracle):
             self.fixed_goal = None
         if agent_xyz is not None:
             # NOTE: reference indexes grid with an ndarray here (msrooms.py:356) and raises;
-            # restated with the evident intent (wall -> START_XYZ). Parity unpinned.
+            # restated with the evident intent (wall -> START_XYZ); device == oracle in
+            # tests/test_grid_edges_gpu.py.
             a = tuple(reversed(agent_xyz))
             if ms[a] == 0:
                 a = tuple(reversed(self.START_XYZ))

@@ -371,3 +371,165 @@ def crooms_table_check_counts(meta, c):
     if float(meta["kwargs"].get("cell_size", 1.0)) == 1.25:
         assert c["cell_reciprocal_differs"] >= 50, c
     assert 2 * c["deterministic"] >= B, c
+
+
+# ---- FourRooms / ROOMS one-step tables (make_golden.py GRID_TABLES) ----
+# Every row is one env: an agent cell, a goal cell, an elapsed count and an intended action (the effective one comes
+# from the stream). Rows: every walkable agent cell (stairs included) x every intended action x the goal replicas x
+# elapsed {0, time_limit - 1, time_limit}. Random-goal tables set the goal per row: the cell the intended action leads
+# to (stair transit included), the neighbour in each of the 4 / 8 observation directions, the agent's own cell and one
+# far cell; a goal that would fall on a cell no goal can take is the far cell instead. Fixed-goal tables keep the
+# configuration's goal and repeat every row `reps` times (other draws). Scalar-obs tables are padded with repeats of
+# their first rows to a multiple of 512, the staged fused kernel's tile.
+def load_grid_table(name):
+    """A `grid_table` case (make_golden.py GRID_TABLES): (index entry, dict of the recorded arrays)."""
+    meta = load_index()["grid_table"][name]
+    with np.load(os.path.join(GOLDEN_DIR, meta["file"]), allow_pickle=False) as z:
+        return meta, {k: z[k] for k in z.files}
+
+
+def grid_table_oracle(meta, B=1):
+    """The numpy oracle of a grid_table case's configuration (its maps, actions and valid cells drive the rows)."""
+    from oracle import gridworld
+    kw = dict(meta["kwargs"])
+    for k in ("goal_xyz", "goal_xy"):
+        if kw.get(k) is not None:
+            kw[k] = tuple(kw[k])
+    cls = gridworld.FourRoomsOracle if meta["kind"] == "fourrooms" else gridworld.RoomsOracle
+    return cls(B, **kw)
+
+
+def grid_table_dirs(meta):
+    """The observation directions of a table: 8 with a Hansen-8 obs or ordinal actions, else 4."""
+    kw = meta["kwargs"]
+    default = "cardinal" if meta["kind"] == "fourrooms" else "ordinal"
+    return 8 if "8" in kw.get("obs_type", "mdp") or kw.get("action_type", default) == "ordinal" else 4
+
+
+def grid_dest(ora, cell, a):
+    """(cell after effective action a, blocked): the move, then the stair transit (msrooms.py:401-404, :419-428)."""
+    prop = tuple(int(v) for v in np.asarray(cell) + ora.actions[a])
+    v = ora.grid[prop]
+    if v == ora.wall_value:
+        return tuple(int(x) for x in cell), True
+    if ora.grid.ndim == 3 and v == 3:
+        return (prop[0] + 1, int(ora.DOWN_YX[0]), int(ora.DOWN_YX[1])), False
+    if ora.grid.ndim == 3 and v == 2:
+        return (prop[0] - 1, int(ora.UP_YX[0]), int(ora.UP_YX[1])), False
+    return prop, False
+
+
+def grid_table_cells(ora):
+    """Every cell an agent can stand on, all floors: coordinates [n, ndim] in flat order."""
+    walk = ora.grid != ora.wall_value
+    return np.array(np.nonzero(walk)).T
+
+
+def grid_table_inputs(meta):
+    """Build the rows of a grid_table case: dict(agent [B, ndim], goal [B, ndim], elapsed [B], action [B], all int64;
+    variant int8 [B]: 0 destination, 1.. the observation directions, -2 own cell, -1 far, -3 fixed goal).
+    Deterministic in meta (kind, kwargs, reps, rows, num_envs)."""
+    ora = grid_table_oracle(meta)
+    shape, nd = ora.grid.shape, ora.grid.ndim
+    tl = int(meta["kwargs"]["time_limit"])
+    nact = ora.actions.shape[0]
+    from oracle.gridworld import ACTIONS_ORDINAL, ACTIONS_ORDINAL_Z
+    dirs = (ACTIONS_ORDINAL_Z if nd == 3 else ACTIONS_ORDINAL)[::8 // grid_table_dirs(meta)]
+    cells = grid_table_cells(ora)
+    fixed = ora.fixed_goal is not None
+    vg = set(int(v) for v in ora.valid_goal)
+    vgc = np.array(np.unravel_index(np.asarray(ora.valid_goal), shape)).T
+    A, G, E, ACT, V = [], [], [], [], []
+    for c in cells:
+        c = tuple(int(v) for v in c)
+        if fixed:
+            goals = [(-3, tuple(int(v) for v in ora.fixed_goal))] * int(meta["reps"])
+            far = None
+        else:
+            dist = np.abs(vgc[:, -2:] - np.array(c[-2:])).sum(-1)
+            far = tuple(int(v) for v in vgc[int(dist.argmax())])
+        els = (0, tl - 1, tl)
+        for a in range(nact):
+            if not fixed:
+                cand = [(0, grid_dest(ora, c, a)[0])]
+                cand += [(1 + j, tuple(int(v) for v in np.array(c) + d)) for j, d in enumerate(dirs)]
+                cand += [(-2, c), (-1, far)]
+                goals = [(v, g if int(np.ravel_multi_index(g, shape)) in vg else far) for v, g in cand]
+            for v, g in goals:
+                for e in els:
+                    A.append(c)
+                    G.append(g)
+                    E.append(e)
+                    ACT.append(a)
+                    V.append(v)
+    out = dict(agent=np.array(A, np.int64).reshape(-1, nd), goal=np.array(G, np.int64).reshape(-1, nd),
+               elapsed=np.array(E, np.int64), action=np.array(ACT, np.int64), variant=np.array(V, np.int8))
+    n = out["elapsed"].size
+    assert n == meta["rows"], (n, meta["rows"])
+    pad = meta["num_envs"] - n
+    assert 0 <= pad < 512
+    if pad:
+        out = {k: np.concatenate((v, v[:pad])) for k, v in out.items()}
+    return out
+
+
+def grid_table_counts(meta, inp, eff, rew, term, trunc):
+    """The counts of one table step from its inputs, the effective actions and the step's outputs (the padding rows
+    excluded)."""
+    ora = grid_table_oracle(meta)
+    kw, n = meta["kwargs"], meta["rows"]
+    term, trunc = np.asarray(term, bool)[:n], np.asarray(trunc, bool)[:n]
+    rew, eff = np.asarray(rew)[:n], np.asarray(eff)[:n]
+    agent, goal = inp["agent"][:n], inp["goal"][:n]
+    nact = ora.actions.shape[0]
+    cells = grid_table_cells(ora)
+    cell_id = {tuple(int(v) for v in c): i for i, c in enumerate(cells)}
+    dest = np.zeros((len(cells), nact), np.int64)
+    blocked = np.zeros((len(cells), nact), bool)
+    onstair = np.zeros((len(cells), nact), bool)
+    for i, c in enumerate(cells):
+        for a in range(nact):
+            d, b = grid_dest(ora, c, a)
+            dest[i, a], blocked[i, a] = np.ravel_multi_index(d, ora.grid.shape), b
+            onstair[i, a] = (not b) and d != tuple(int(v) for v in c + ora.actions[a])
+    ci = np.array([cell_id[tuple(int(v) for v in c)] for c in agent])
+    seen = np.zeros((len(cells), nact), bool)
+    seen[ci, eff] = True
+    need = np.array([[(dest[i] != dest[i, a]).any() for a in range(nact)] for i in range(len(cells))])
+    row_blocked, row_stair = blocked[ci, eff], onstair[ci, eff]
+    on_goal = (agent == goal).all(-1)
+    stepped = agent + ora.actions[eff]  # the cell moved onto, before any stair transit
+    c = dict(rows=int(n), cells=int(len(cells)), pairs_needed=int(need.sum()), pairs_seen=int((need & seen).sum()),
+             term_only=int((term & ~trunc).sum()), trunc_only=int((trunc & ~term).sum()),
+             both=int((term & trunc).sum()), neither=int((~term & ~trunc).sum()),
+             blocked=int(row_blocked.sum()),
+             blocked_on_goal=int((row_blocked & on_goal & term & (rew == np.float32(kw["goal_reward"]))).sum()),
+             wall_reward=int((rew == np.float32(kw["wall_reward"])).sum()),
+             stair_transits=int(row_stair.sum()),
+             stair_is_goal_not_term=int((row_stair & (stepped == goal).all(-1) & ~term).sum()),
+             stair_onto_goal_term=int((row_stair & term).sum()))
+    return c
+
+
+GRID_UNIFORM_P = {4: 0.75, 8: 0.875}  # every effective action has probability 1 / n
+
+
+def grid_table_check_counts(meta, c):
+    """The conditions every grid_table case was built to meet (asserted by the generator and by the CPU test)."""
+    ora = grid_table_oracle(meta)
+    kw = meta["kwargs"]
+    nact = ora.actions.shape[0]
+    assert c["rows"] == meta["rows"], c
+    assert c["rows"] >= c["cells"] * nact * 12, c  # >= 48 / 96 rows per cell
+    if kw["action_failure_probability"] == GRID_UNIFORM_P[nact]:
+        assert c["pairs_seen"] == c["pairs_needed"] > 0, c
+    assert min(c["term_only"], c["trunc_only"], c["both"], c["neither"]) >= 1, c
+    if meta.get("no_blocked_on_goal"):  # a fixed goal with eight walkable neighbours under ordinal actions
+        assert c["blocked_on_goal"] == 0, c
+    else:
+        assert c["blocked_on_goal"] >= 1, c
+    assert c["wall_reward"] >= 1 and c["blocked"] >= c["wall_reward"] + c["blocked_on_goal"], c
+    if ora.grid.ndim == 3 and ora.grid.shape[0] > 1:
+        assert c["stair_transits"] >= 1, c
+        if ora.fixed_goal is None:
+            assert c["stair_is_goal_not_term"] >= 1 and c["stair_onto_goal_term"] >= 1, c

@@ -15,6 +15,10 @@ reference step over every (state, action) row of a Taxi map instead of a traject
 The `crooms_table` group (CROOMS_TABLES, files crooms_table_*.npz, `python tests/golden/make_golden.py crooms_table`)
 is one reference step of C-ROOMS over rows aimed at the lines where a step decides something (cell boundaries, the
 goal circle, the clips, the time limit): see run_crooms_table and fixtures.crooms_table_inputs.
+
+The `grid_table` group (GRID_TABLES, files grid_table_*.npz, `python tests/golden/make_golden.py grid_table`) is one
+reference step of FourRooms / ROOMS over every (agent cell, intended action) with the goal and the elapsed count placed
+where a step decides something: see run_grid_table and fixtures.grid_table_inputs.
 """
 import os
 import sys
@@ -344,6 +348,164 @@ def run_crooms_table(m, name, spec):
     return meta
 
 
+# ---- FourRooms / ROOMS one-step tables: every (agent cell, intended action) x goal and elapsed replicas ----
+# name: (kind, ctor kwargs, extra index fields). time_limit 3 and dyadic rewards that tell goal, wall and step apart.
+# Most tables use the uniform failure matrix (p = 0.75 cardinal, 0.875 ordinal: every effective action has probability
+# 1 / n), so that the reference's own stream reaches every (cell, effective action); three keep the default
+# probabilities, two have p = 0 (the effective action is the intended one: the philox kernels can run them too).
+# The seed is the first below 64 at which the reference's step meets fixtures.grid_table_check_counts.
+_GT = dict(time_limit=3, goal_reward=2.0, wall_reward=-1.0, step_reward=-0.25)
+_U4, _U8 = dict(action_failure_probability=0.75), dict(action_failure_probability=0.875)
+GRID_TABLES = {
+    # the headline configuration: fixed goal, scalar Hansen obs, default failure probability (the windowed kernel)
+    "grid_table_fr_z1_hansen_fixed": (FR, dict(grid_z=1, obs_type="hansen", action_failure_probability=1.0 / 3, **_GT),
+                                      dict(reps=4)),
+    "grid_table_fr_z1_hansen8_ord": (FR, dict(grid_z=1, obs_type="hansen8", action_type="ordinal", goal_xyz=None,
+                                              **_U8, **_GT), {}),
+    "grid_table_fr_z3_hansen": (FR, dict(grid_z=3, obs_type="hansen", goal_xyz=None, **_U4, **_GT), {}),
+    "grid_table_fr_z2_vgh8": (FR, dict(grid_z=2, obs_type="vector_goal_hansen8", goal_xyz=None, **_U4, **_GT), {}),
+    "grid_table_fr_z2_goal_mdp_p0": (FR, dict(grid_z=2, obs_type="goal_mdp", goal_xyz=None,
+                                              action_failure_probability=0.0, **_GT), {}),
+    "grid_table_fr_z2_vgmdp_ord": (FR, dict(grid_z=2, obs_type="vector_goal_mdp", action_type="ordinal", goal_xyz=None,
+                                            action_failure_probability=1.0 / 3, **_GT), {}),
+    "grid_table_rooms_4_mdp_ord": (RO, dict(layout="4", obs_type="mdp", goal_xy=None, **_U8, **_GT), {}),
+    "grid_table_rooms_4_vmdp_card": (RO, dict(layout="4", obs_type="vector_mdp", action_type="cardinal", goal_xy=None,
+                                              **_U4, **_GT), {}),
+    # fixed goal on a cell with eight walkable neighbours, default failure probability 0.2 (the windowed kernel)
+    "grid_table_rooms_4_hansen_fixed": (RO, dict(layout="4", obs_type="hansen", goal_xy=(4, 4),
+                                                 action_failure_probability=0.2, **_GT),
+                                        dict(reps=4, no_blocked_on_goal=1)),
+    "grid_table_rooms_8b_grid5_card": (RO, dict(layout="8b", obs_type="grid", obs_n=5, action_type="cardinal",
+                                                goal_xy=None, **_U4, **_GT), {}),
+    "grid_table_rooms_4b_grid3_ord": (RO, dict(layout="4b", obs_type="grid", obs_n=3, goal_xy=None, **_U8, **_GT), {}),
+    "grid_table_rooms_16_goal_room_p0": (RO, dict(layout="16", obs_type="goal_room", action_type="cardinal",
+                                                  goal_xy=None, action_failure_probability=0.0, **_GT), {}),
+    "grid_table_rooms_4b_room_card": (RO, dict(layout="4b", obs_type="room", action_type="cardinal", goal_xy=None,
+                                               **_U4, **_GT), {}),
+    "grid_table_rooms_4_vhansen_ord": (RO, dict(layout="4", obs_type="vector_hansen", goal_xy=None, **_U8, **_GT), {}),
+}
+GRID_TABLE_MAX_BYTES = 384 * 1024
+
+
+def _narrow_int(x):
+    x = np.asarray(x)
+    assert np.array_equal(x, np.round(x))
+    lo, hi = int(x.min()), int(x.max())
+    for dt in (np.uint8, np.int8, np.uint16, np.int16, np.int32):
+        if np.iinfo(dt).min <= lo and hi <= np.iinfo(dt).max:
+            return x.astype(dt)
+    raise AssertionError((lo, hi))
+
+
+def _lemire_rejections(pre, post, B, counts):
+    """Rejected Lemire draws among the step's reset draws: the stream walked from the pre-step state over random(B)
+    and the choice() calls of `counts` = [(range, draws), ...]; the walk must end on the recorded post-step state."""
+    from oracle.pcg64 import PCG64
+    g = PCG64((int(pre[0]) << 64) | int(pre[1]), (int(pre[2]) << 64) | int(pre[3]), int(pre[4]), int(pre[5]))
+    g.advance(B)
+    calls, draws, next32 = [0], 0, g.next32
+
+    def counted():
+        calls[0] += 1
+        return next32()
+    g.next32 = counted
+    for n, b in counts:
+        if n > 1:  # choice over one element draws nothing
+            draws += b
+            for _ in range(b):
+                g.lemire32(n)
+    assert [g.state >> 64, g.state & ((1 << 64) - 1), g.has_uint32] == [int(post[0]), int(post[1]), int(post[4])]
+    return calls[0] - draws
+
+
+def _has_lemire_rejection(pre, post, B, halves):
+    """Whether the step's reset draws held a rejected Lemire draw: without one the stream moves by random(B) and
+    exactly `halves` half-words (numpy's buffered half first), which is compared with the recorded post-step state."""
+    from oracle.pcg64 import PCG64
+    g = PCG64((int(pre[0]) << 64) | int(pre[1]), (int(pre[2]) << 64) | int(pre[3]), int(pre[4]), int(pre[5]))
+    g.advance(B)
+    has = g.has_uint32
+    if halves and has:
+        halves, has = halves - 1, 0
+    g.advance((halves + 1) // 2)
+    has = halves % 2 if halves else has
+    return [g.state >> 64, g.state & ((1 << 64) - 1), has] != [int(post[0]), int(post[1]), int(post[4])]
+
+
+def run_grid_table(m, name, spec):
+    """reset(seed), overwrite agent / goal / elapsed with the table's rows (fixtures.grid_table_inputs), one step on
+    the reference's own stream. Recorded: the four outputs, the post-step agent / goal / elapsed (the reference's own
+    reset draws included), the PCG64 state before and after the step. The effective actions are the oracle's, which
+    must first reproduce the reference's step bit for bit from the same state: the reference does not expose them."""
+    from fixtures import (grid_table_cells, grid_table_check_counts, grid_table_counts, grid_table_dirs,
+                          grid_table_inputs, grid_table_oracle)
+    from grid_table_oracle import table_oracle_step
+    kind, kw, extra = spec
+    kw = {k: (list(v) if isinstance(v, tuple) else v) for k, v in kw.items()}
+    meta = dict(kind=kind, kwargs=kw, numpy=np.__version__, file=f"{name}.npz", **extra)
+    ora1 = grid_table_oracle(meta)
+    fixed = ora1.fixed_goal is not None
+    nact, ncell = ora1.actions.shape[0], len(grid_table_cells(ora1))
+    meta["num_actions"] = nact
+    meta["rows"] = ncell * nact * 3 * (meta["reps"] if fixed else grid_table_dirs(meta) + 3)
+    scalar = not ("vector" in kw["obs_type"] or "grid" in kw["obs_type"])
+    meta["num_envs"] = B = -(-meta["rows"] // 512) * 512 if scalar else meta["rows"]
+    inp = grid_table_inputs(meta)
+    an, gn = ("agent_zyx", "goal_zyx") if kind == FR else ("agent_yx", "goal_yx")
+    # Every seed below 64 is stepped by the reference. The first seed that meets the conditions is taken, unless a
+    # later one meets them AND holds a Lemire rejection among its reset draws: then that one. The index records how
+    # many of the 64 seeds had a rejection (`lemire_scan`; none: the case stays with the planted rejections of
+    # tests/test_grid_gpu.py and tests/test_wgrid_gpu.py). Seeds that cannot be taken are stepped by the reference only.
+    best, with_rej = None, 0
+    ng, na = (0 if fixed else len(ora1.valid_goal)), len(ora1.valid_agent)
+    for seed in range(64):
+        meta["seed"] = seed
+        env = make_env(m, kind, {k: (tuple(v) if isinstance(v, list) else v) for k, v in kw.items()}, B)
+        env.reset(seed=seed)
+        pre = _rng6(env.np_random)
+        if fixed:
+            assert np.array_equal(getattr(env, gn), inp["goal"]), (getattr(env, gn)[0], inp["goal"][0])
+        setattr(env, an, inp["agent"].copy())
+        setattr(env, gn, inp["goal"].copy())
+        env.elapsed = inp["elapsed"].copy()
+        o, r, d, tr, _ = env.step(inp["action"].copy())
+        o = np.asarray(o)
+        assert r.dtype == np.float32
+        arrays = dict(obs=_narrow_int(o), rew=r, term=np.asarray(d, bool), trunc=np.asarray(tr, bool),
+                      agent=_narrow_int(getattr(env, an)), goal=_narrow_int(getattr(env, gn)),
+                      elapsed=_narrow_int(env.elapsed), pre_rng_state=pre, rng_state=_rng6(env.np_random))
+        nres = int((arrays["term"] | arrays["trunc"]).sum())
+        rejected = _has_lemire_rejection(pre, arrays["rng_state"], B, nres * ((ng > 1) + (na > 1)))
+        with_rej += rejected
+        if best is not None and not rejected:
+            continue
+        ora, out, eff = table_oracle_step(meta, inp, pre)
+        for k, v in dict(obs=out[0], rew=out[1], term=out[2], trunc=out[3], agent=ora.agent, goal=ora.goal,
+                         elapsed=ora.elapsed).items():
+            assert np.array_equal(np.asarray(v).astype(np.float64), arrays[k].astype(np.float64)), (name, k)
+        assert np.array_equal(_rng6(ora.gen), arrays["rng_state"])
+        counts = grid_table_counts(meta, inp, eff, r, d, tr)
+        counts["resets"] = nres
+        counts["lemire_rejections"] = _lemire_rejections(pre, arrays["rng_state"], B, [(ng, nres), (na, nres)])
+        assert (counts["lemire_rejections"] > 0) == rejected
+        try:
+            grid_table_check_counts(meta, counts)
+        except AssertionError:
+            continue
+        if best is None or (counts["lemire_rejections"] and not best[2]["lemire_rejections"]):
+            best = (seed, arrays, counts)
+        if best[2]["lemire_rejections"]:
+            break
+    if best is None:
+        raise AssertionError(f"{name}: no seed below 64 meets the table's conditions: {counts}")
+    meta["seed"], arrays, meta["counts"] = best
+    meta["lemire_scan"] = dict(seeds=seed + 1, seeds_with_rejection=int(with_rej))
+    path = os.path.join(HERE, meta["file"])
+    np.savez_compressed(path, **arrays)
+    assert os.path.getsize(path) <= GRID_TABLE_MAX_BYTES, os.path.getsize(path)
+    return meta
+
+
 def main():
     import json
     prefix = sys.argv[1] if len(sys.argv) > 1 else ""
@@ -370,6 +532,12 @@ def main():
         t0 = time.time()
         index.setdefault("crooms_table", {})[name] = run_crooms_table(m, name, spec)
         print(f"{name}: {time.time() - t0:.1f}s {index['crooms_table'][name]['counts']}", flush=True)
+    for name, spec in GRID_TABLES.items():
+        if not name.startswith(prefix):
+            continue
+        t0 = time.time()
+        index.setdefault("grid_table", {})[name] = run_grid_table(m, name, spec)
+        print(f"{name}: {time.time() - t0:.1f}s {index['grid_table'][name]['counts']}", flush=True)
     if prefix in ("", "taxi_reset_hist"):
         t0 = time.time()
         index["taxi_reset_hist"] = taxi_reset_histogram(m)
