@@ -139,9 +139,12 @@ __device__ __forceinline__ StepOut cf_dyn(const CfDev& p, CfEnv& e, double a64, 
   return o;
 }
 
-__device__ void cf_metrics(const CfDev& p, float rsum, uint32_t eps, uint32_t lens, uint32_t nst) {
+// lens is 64-bit from the thread on: one episode can be 2^29 steps long (MAX_TIME_LIMIT), so four envs of a thread
+// that end together already sum to 2^31 and two such threads wrapped a 32-bit wave sum to 0.
+__device__ void cf_metrics(const CfDev& p, float rsum, uint32_t eps, unsigned long long lens, uint32_t nst) {
   __shared__ float s_r[WAVES];
-  __shared__ uint32_t s_e[WAVES], s_l[WAVES], s_n[WAVES];
+  __shared__ uint32_t s_e[WAVES], s_n[WAVES];
+  __shared__ unsigned long long s_l[WAVES];
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
@@ -202,7 +205,8 @@ __global__ __launch_bounds__(TPB) void cf_rollout(CfDev p, int K, uint64_t step0
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float4* wv = s_obs + wid * 64 * 3;
   float rsum = 0.f;
-  uint32_t eps = 0, lens = 0, nst = 0;
+  uint32_t eps = 0, nst = 0;
+  unsigned long long lens = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;
     CfEnv e[EPT];
@@ -245,7 +249,7 @@ __global__ __launch_bounds__(TPB) void cf_rollout(CfDev p, int K, uint64_t step0
           rsum += o.rew;
           if (o.term | o.trunc) {
             eps += 1u;
-            lens += e[i].w >> 2;
+            lens += (unsigned long long)(e[i].w >> 2);
             if constexpr (MODE == M_NUMPY) {
               e[i].w = (e[i].w & 3u) | (EL_PENDING << 2);
             } else if constexpr (MODE == M_REPLAY) {

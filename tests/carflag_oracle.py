@@ -54,6 +54,53 @@ class FollowDraws:
         return self.x[idx], self.hv[idx], self.pr[idx]
 
 
+def dynamics(s, heavens, priests, a, madd=lambda v, f, c: v + f * c, term_of=lambda x: np.abs(x) >= 1.0,
+             zone_of=lambda xd, pr: (xd >= pr - 0.2) & (xd <= pr + 0.2), side_of=lambda x0, x: np.sign(x)):
+    """The arithmetic of one step from the state s [B, 3] (elapsed and the reset excluded): (v', x', terminated,
+    reward, direction). float32 actions: float32 arithmetic with the constants rounded to float32; anything else
+    (float64, or values of the float64 table): float64 arithmetic from the f32 state, rounded when stored. The four
+    keyword pieces are the rules themselves; the table generator swaps one at a time for a wrong one to count the
+    rows that would notice (tests/golden/make_golden_carflag.py VARIANTS)."""
+    if a.dtype == F32:
+        f = np.minimum(np.maximum(a, F32(-1.0)), F32(1.0))
+        v = np.minimum(np.maximum(madd(s[:, 1], f, F32(0.0015)), F32(-0.07)), F32(0.07))
+        x = np.minimum(np.maximum(s[:, 0] + v, F32(-1.1)), F32(1.1))
+        assert v.dtype == F32 and x.dtype == F32
+    else:
+        f = np.minimum(np.maximum(a.astype(np.float64), -1.0), 1.0)
+        v = np.minimum(np.maximum(madd(s[:, 1].astype(np.float64), f, 0.0015), -0.07), 0.07)
+        x = np.minimum(np.maximum(s[:, 0].astype(np.float64) + v, -1.1), 1.1)
+    term = term_of(x)
+    side = side_of(s[:, 0], x).astype(F32)
+    rew = np.where(term, np.where(side == heavens, F32(1), F32(-1)), F32(0)).astype(F32)
+    direction = np.where(zone_of(x.astype(np.float64), priests), heavens, F32(0)).astype(F32)
+    return v, x, term, rew, direction
+
+
+PHILOX_TAG = 0x63666c31  # 'cfl1'
+
+
+class PhiloxDraws:
+    """rng_mode="philox" predicted from the key alone: the reset of env e at counter c takes the four words of the
+    Philox block (e, c, tag 'cfl1'): k53 = (w1 << 32 | w0) >> 11, heaven = w2 >> 31, priest = w3 >> 31. `reset(seed)`
+    uses counter 0; every step and every further `reset()` the next one. The caller sets `.counter` before the
+    oracle call that may reset (`PhiloxDraws(philox_key(seed))`, oracle.philox)."""
+
+    def __init__(self, key):
+        self.key, self.counter = key, 0
+
+    def draw(self, idx):
+        from oracle.philox import env_step_words
+        w0, w1, w2, w3 = (w[idx] for w in env_step_words(int(idx[-1]) + 1, self.counter, PHILOX_TAG, self.key))
+        k = ((w1.astype(np.uint64) << np.uint64(32)) | w0.astype(np.uint64)) >> np.uint64(11)
+        return k, (w2 >> np.uint32(31)).astype(np.int64), (w3 >> np.uint32(31)).astype(np.int64)
+
+    def values(self, idx):
+        k, h, p = self.draw(idx)
+        self.last = (k, h, p)
+        return reset_position(k), np.where(h > 0, 1.0, -1.0).astype(F32), np.where(p > 0, 0.5, -0.5)
+
+
 class CarFlagOracle:
     def __init__(self, num_envs, time_limit=160, num_actions=None, draws=None):
         self.B = num_envs
@@ -89,28 +136,13 @@ class CarFlagOracle:
         return self.s.copy()
 
     def step(self, actions):
-        """float32 actions: float32 arithmetic with the constants rounded to float32; anything else (float64,
-        or indices into the float64 table): float64 arithmetic from the f32 state, rounded when stored."""
+        """One step of every env (see `dynamics`), then the same-step reset of the finished ones."""
         a = np.asarray(actions).reshape(-1)
         if self.table is not None:
             a = self.table[a]
         self.elapsed += 1
-        if a.dtype == F32:
-            f = np.minimum(np.maximum(a, F32(-1.0)), F32(1.0))
-            v = np.minimum(np.maximum(self.s[:, 1] + f * F32(0.0015), F32(-0.07)), F32(0.07))
-            x = np.minimum(np.maximum(self.s[:, 0] + v, F32(-1.1)), F32(1.1))
-            assert v.dtype == F32 and x.dtype == F32
-        else:
-            f = np.minimum(np.maximum(a.astype(np.float64), -1.0), 1.0)
-            v = np.minimum(np.maximum(self.s[:, 1].astype(np.float64) + f * 0.0015, -0.07), 0.07)
-            x = np.minimum(np.maximum(self.s[:, 0].astype(np.float64) + v, -1.1), 1.1)
-        term = np.abs(x) >= 1.0
-        side = np.sign(x).astype(F32)
-        rew = np.where(term, np.where(side == self.heavens, F32(1), F32(-1)), F32(0)).astype(F32)
+        v, x, term, rew, direction = dynamics(self.s, self.heavens, self.priests, a)
         trunc = self.elapsed >= self.time_limit
-        xd = x.astype(np.float64)
-        zone = (xd >= self.priests - 0.2) & (xd <= self.priests + 0.2)
-        direction = np.where(zone, self.heavens, F32(0)).astype(F32)
         keep = ~term
         self.s[keep, 0] = x[keep].astype(F32)
         self.s[keep, 1] = v[keep].astype(F32)
@@ -190,11 +222,52 @@ def load_render():
     return np.load(os.path.join(here, idx["carflag_render"]["file"]), allow_pickle=False)
 
 
-def final_rng_state(meta):
-    """The recorded final PCG64 state as numpy's bit_generator.state dict."""
-    r = meta["final_rng"]
+def rng_state(r):
+    """A recorded PCG64 state ({state, inc, has_uint32, uinteger}, the big integers as strings) as numpy's
+    bit_generator.state dict."""
     return {"bit_generator": "PCG64", "state": {"state": int(r["state"]), "inc": int(r["inc"])},
             "has_uint32": r["has_uint32"], "uinteger": r["uinteger"]}
+
+
+def final_rng_state(meta):
+    """The recorded final PCG64 state as numpy's bit_generator.state dict."""
+    return rng_state(meta["final_rng"])
+
+
+# ---------------------------------------------------------------- one-step tables ----
+TABLE_NAMES = ("carflag_table_f32", "carflag_table_f64", "carflag_table_disc2", "carflag_table_disc4",
+               "carflag_table_disc5")
+
+
+def load_table(name):
+    """(meta, arrays) of one one-step table (carflag_index.json `tables`): ONE reference step of a B-row env whose
+    rows were planted (s0, elapsed0, heavens0, priests0) after a seeded reset, with the action `act`, the reference's
+    obs / rew / term / trunc, its state after the step (final_*) and the draws of the rows that reset."""
+    import os
+    here, idx = load_index()
+    meta = idx["tables"][name]
+    return meta, dict(np.load(os.path.join(here, meta["file"]), allow_pickle=False))
+
+
+def table_oracle(meta, d, draws):
+    """The oracle with a table's rows planted."""
+    ora = CarFlagOracle(meta["rows"], meta["time_limit"], meta.get("num_actions"), draws)
+    ora.s[:] = d["s0"]
+    ora.elapsed[:] = d["elapsed0"]
+    ora.heavens[:] = d["heavens0"]
+    ora.priests[:] = d["priests0"]
+    return ora
+
+
+def bits_equal(got, want):
+    """Elementwise: the same bits, or a NaN where `want` (the reference) holds a NaN. float32 / float64 by their
+    bits (so -0.0 != 0.0), everything else by value."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
+    if want.dtype.kind != "f":
+        return got == want
+    u = {4: np.uint32, 8: np.uint64}[want.dtype.itemsize]
+    return np.where(np.isnan(want), np.isnan(got), got.view(u) == want.view(u))
 
 
 CASE_NAMES = ("carflag_f32_b64", "carflag_f32_tl40_b63", "carflag_f64_b64", "carflag_disc5_b64")
