@@ -304,6 +304,9 @@ int gp_create(int kind, const void* config, int64_t num_envs, int device, int rn
     case GP_KIND_ROCKSAMPLE:
       be = make_rocksample_backend((const gp_rocksample_config*)config, num_envs, device, rng_mode, &err);
       break;
+    case GP_KIND_HEAVENHELL:
+      be = make_heavenhell_backend((const gp_heavenhell_config*)config, num_envs, device, rng_mode, &err);
+      break;
     default: gp_set_error("gp_create: unknown kind %d", kind); return GP_E_INVALID;
   }
   if (!be) return err ? err : GP_E_INVALID;

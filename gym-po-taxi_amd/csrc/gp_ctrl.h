@@ -6,7 +6,8 @@
 #include "../../include/gym_po_amd.h"
 #include "gp_common.h"
 
-// the env draws carry 0x67706f21 (grid) / 0x726f636b (rocksample) / 0x616e7431 (anttag) / 0x74617869 (taxi)
+// the env draws carry 0x67706f21 (grid) / 0x726f636b (rocksample) / 0x616e7431 (anttag) / 0x74617869 (taxi) /
+// 0x6868656c (heavenhell)
 constexpr uint32_t CTRL_TAG = 0x67706f63u;
 // Largest dynamic LDS per block (env tables + controller table) up to which the kinds that stage the table in LDS
 // (grid.hip, taxi.hip) do so by default; the knob ctrl_lds_max overrides it, up to 60 KB.

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("GYM_PO_AMD_LIB", os.path.join(_HERE, "libgympo_amd.so
 GP_OK = 0
 GP_E_DEVICE = -5
 GP_KIND_GRID, GP_KIND_TAXI, GP_KIND_CROOMS, GP_KIND_ANTTAG, GP_KIND_CARFLAG, GP_KIND_ROCKSAMPLE = 1, 2, 3, 4, 5, 6
+GP_KIND_HEAVENHELL = 7
 GP_RNG_NUMPY, GP_RNG_PHILOX, GP_RNG_REPLAY = 0, 1, 2
 RNG_MODES = {"numpy": GP_RNG_NUMPY, "philox": GP_RNG_PHILOX, "replay": GP_RNG_REPLAY}
 GP_DTYPE_I32, GP_DTYPE_U8, GP_DTYPE_F32, GP_DTYPE_F64 = 0, 1, 2, 3
@@ -72,6 +73,13 @@ class RockSampleConfig(ctypes.Structure):
                 ("obs_cell", ctypes.c_int32), ("time_limit", ctypes.c_int32), ("exit_reward", ctypes.c_float),
                 ("good_reward", ctypes.c_float), ("bad_reward", ctypes.c_float), ("empty_reward", ctypes.c_float),
                 ("check_reward", ctypes.c_float), ("step_reward", ctypes.c_float), ("wall_reward", ctypes.c_float)]
+
+
+class HeavenHellConfig(ctypes.Structure):
+    _fields_ = [("height", ctypes.c_int32), ("width", ctypes.c_int32), ("flags", ctypes.POINTER(ctypes.c_uint8)),
+                ("obs_base", _i32p), ("obs_base_n", ctypes.c_int32), ("keep_thr", ctypes.c_uint32),
+                ("time_limit", ctypes.c_int32), ("heaven_reward", ctypes.c_float), ("hell_reward", ctypes.c_float),
+                ("step_reward", ctypes.c_float), ("wall_reward", ctypes.c_float)]
 
 
 # every symbol include/gym_po_amd.h declares: name -> (restype, argtypes)

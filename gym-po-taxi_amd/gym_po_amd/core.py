@@ -290,10 +290,10 @@ class NativeVecEnv:
     def set_controller(self, probs=None, thresholds=None):
         """Install the tabular controller of the closed-loop rollouts (FourRooms / ROOMS with a scalar obs in
         rng_mode='philox', RockSample, where A * M may not exceed 64, AntTagGridEnv with obs_type='index' in
-        rng_mode='philox', and TaxiVecEnv with hansen_obs=True in rng_mode='philox', scalar or one-hot: the table is
-        indexed by the scalar Hansen obs either way), or remove it when both arguments are None. `probs`: float
-        [M, n_obs, A, M], the joint probability of (action, next node) given (node, obs), or [n_obs, A] for a
-        memoryless policy; lowered by `controller.controller_thresholds`. `thresholds`: that uint32
+        rng_mode='philox', TaxiVecEnv with hansen_obs=True in rng_mode='philox', scalar or one-hot: the table is
+        indexed by the scalar Hansen obs either way, and HeavenHellGridEnv with either obs_type), or remove it when
+        both arguments are None. `probs`: float [M, n_obs, A, M], the joint probability of (action, next node) given
+        (node, obs), or [n_obs, A] for a memoryless policy; lowered by `controller.controller_thresholds`. `thresholds`: that uint32
         [M, n_obs, A * M] table itself. n_obs is `single_observation_space.n` (a one-hot Taxi's row width `no`), A the
         action count, M <= 8. Every env's node becomes 0. Raises GymPoError for a table that does not fit the env or
         is not monotone up to 2^31, and for envs without closed-loop rollouts."""
@@ -325,7 +325,8 @@ class NativeVecEnv:
     _SCORE_FIELDS = ("episodes", "return_sum", "length_sum", "env_steps", "discounted_return_sum")
 
     def set_controller_population(self, probs=None, thresholds=None, group_envs=None, gamma=1.0):
-        """Install P controllers side by side (FourRooms / ROOMS with a scalar obs in rng_mode='philox'), or remove
+        """Install P controllers side by side (FourRooms / ROOMS with a scalar obs in rng_mode='philox'; every other
+        env, HeavenHellGridEnv included, raises GymPoError), or remove
         whatever controller is installed when `probs` and `thresholds` are both None. Env e is driven by controller
         e // group_envs; `controller_scores()` then gives one score row per controller, its discounted return under
         `gamma` (float32, in (0, 1]) included. `probs`: float [P, M, n_obs, A, M], lowered by

@@ -20,6 +20,8 @@
  *                                                                gym_po/envs/car_flag.py:50-85, :289-299
  *   gp_create(GP_KIND_ROCKSAMPLE) RockSample (the reference has only the Obs / ACTION enums and a constructor
  *                             signature; the rules are build-defined) gym_po/envs/rocksample/rocksample.py
+ *   gp_create(GP_KIND_HEAVENHELL) AntHeavenHellEnv task rules (grid restatement, build-defined)
+ *                                                                gym_po/envs/ant_heaven_hell.py:35-40, :99-137
  *   gp_seed / gp_seed_words   gymnasium Env.reset(seed=) -> seeding.np_random(seed)
  *                             (msrooms.py:376, rooms.py:184, extended_taxi.py:239, crooms.py:246-249)
  *   gp_reset                  *.reset()      msrooms.py:369-381, rooms.py:177-189,
@@ -60,6 +62,7 @@ extern "C" {
 #define GP_KIND_ANTTAG 4
 #define GP_KIND_CARFLAG 5 /* Car-Flag: 1-D heaven/hell POMDP (car_flag.py) */
 #define GP_KIND_ROCKSAMPLE 6 /* RockSample (Smith & Simmons 2004), build-defined rules: gp_rocksample_config */
+#define GP_KIND_HEAVENHELL 7 /* grid Heaven-Hell (the task of ant_heaven_hell.py), build-defined rules: gp_heavenhell_config */
 
 /* ---- RNG modes ---- */
 #define GP_RNG_NUMPY 0   /* seed-identical to numpy Generator(PCG64(SeedSequence(seed))): GRID, CROOMS, TAXI, CARFLAG */
@@ -201,6 +204,42 @@ typedef struct gp_rocksample_config {
   float exit_reward, good_reward, bad_reward, empty_reward, check_reward, step_reward, wall_reward;
 } gp_rocksample_config;
 
+/* Grid Heaven-Hell (GP_KIND_HEAVENHELL; GP_RNG_PHILOX only: there is no reference stream, so GP_RNG_NUMPY /
+ * GP_RNG_REPLAY return GP_E_UNSUPPORTED). A build-defined grid restatement of the task of the reference's
+ * AntHeavenHellEnv (ant_heaven_hell.py:35-40 the heaven / hell / priest points and the radius, :99-119 the reset with a
+ * fair coin for the heaven side, :121-137 the step; walls and start box: assets/ant_heaven_hell.xml:72-100 and
+ * ant_heaven_hell.py:74). The reference env is a MuJoCo ant: parity with it is unpinned by construction.
+ *   maze     height x width cells, 1 <= height, width <= 16, cell = row * width + col, north is row - 1; one flag
+ *            byte per cell: 0 wall, else 1 (free) plus at most one of 2 (left area) / 4 (right area) / 8 (priest
+ *            area), plus 16 (start cell). A start cell is in neither the left nor the right area.
+ *   state    per env the agent cell, the heaven side (0 = the left area is heaven, 1 = the right) and elapsed;
+ *            gp_get_state / gp_set_state exchange them as int32 [B] each (set clamps the cell to the grid and elapsed
+ *            to [0, 65535] and keeps the low bit of the side; NULL leaves a field alone).
+ *   actions  0 N, 1 E, 2 S, 3 W; [-4, 0) wraps as numpy indexing does; anything else is flagged (GP_E_DEVICE from
+ *            gp_check) and clamped.
+ *   draws    one Philox4x32-10 block per (env, step), counter (env, step_lo, step_hi, 0x6868656c) under the handle's
+ *            key: y = x0 >> 1, the action slips iff y >= keep_thr, to (a + 1 + ((uint64)x1 * 3 >> 32)) & 3; a reset
+ *            takes the start cell starts[((uint64)x2 * n_start) >> 32] (the start cells ascending) and the side
+ *            x3 & 1. gp_reset draws from the block of its own step index.
+ *   step     the move goes to the neighbour cell; off the grid or a wall: the agent stays, wall_reward; else
+ *            step_reward. After the move a cell in the left or right area terminates, and the reward is replaced by
+ *            heaven_reward if that area is the heaven side, else hell_reward. truncated = elapsed + 1 >= time_limit,
+ *            independent of terminated. An episode end resets the env in the same step (draws of the same block).
+ *   obs      int32 [B], taken after the autoreset: obs_base[cell] * 3 + signal, signal 0 outside the priest area,
+ *            inside it 1 = heaven left, 2 = heaven right; n_obs = obs_base_n * 3.
+ * GP_E_INVALID, naming the fault: a side outside [1, 16], a flag byte outside the set above, no start cell, a start
+ * cell in the left or right area, an obs_base entry outside [0, obs_base_n), obs_base_n outside [1, 256], keep_thr
+ * above 2^31, time_limit outside [1, 65535] (elapsed is kept in 16 bits). */
+typedef struct gp_heavenhell_config {
+  int32_t height, width;
+  const uint8_t* flags;       /* [height * width] flag bytes                                          */
+  const int32_t* obs_base;    /* [height * width] the obs base of each cell (the cell, a Hansen code) */
+  int32_t obs_base_n;         /* obs_base values lie in [0, obs_base_n); at most 256                  */
+  uint32_t keep_thr;          /* floor((1 - action_failure_probability) * 2^31); 2^31 = never slips   */
+  int32_t time_limit;
+  float heaven_reward, hell_reward, step_reward, wall_reward;
+} gp_heavenhell_config;
+
 typedef struct gp_env gp_env;
 
 const char* gp_last_error(void);
@@ -248,8 +287,8 @@ void gp_plan_destroy(gp_plan* plan);
 
 /* ---- closed-loop rollouts: a tabular finite-state controller evaluated inside the rollout kernel ----
  * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), ROCKSAMPLE (either obs), ANTTAG with the
- * index obs (obs_index = 1) in GP_RNG_PHILOX, and TAXI with the Hansen obs (GP_OBS_HANSEN, one_hot 0 or 1) in
- * GP_RNG_PHILOX; every other kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
+ * index obs (obs_index = 1) in GP_RNG_PHILOX, TAXI with the Hansen obs (GP_OBS_HANSEN, one_hot 0 or 1) in
+ * GP_RNG_PHILOX, and HEAVENHELL (any obs base); every other kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
  * one step() per action.)
  *
  * The controller has M = n_nodes nodes (1..8; M = 1 is a memoryless policy obs -> action distribution). With A the
@@ -282,6 +321,10 @@ void gp_plan_destroy(gp_plan* plan);
  * whose episode continues (a goal move with num_passengers > 1) does not reset the node. n_obs is the caller's (the
  * Hansen obs space has 16 * n_locs * (n_locs + 1) values). The table is staged in LDS when the env's tables plus the
  * table fit the "ctrl_lds_max" budget below (5 x 5 map: M = 1), else read from global memory.
+ * HEAVENHELL: the obs is that of the state word; the env draws carry 0x6868656c. A = 4, so rows hold exactly L = 4 M <= 32
+ * entries, whole 16-B quads: nothing is padded. n_obs is the caller's (the obs space has obs_base_n * 3 values). The
+ * table is staged in LDS behind the env's tables when both fit the "ctrl_lds_max" budget (the 48-value Hansen obs:
+ * M = 2 is 3 KB, M = 5 is 18.75 KB; M = 8, 48 KB, needs the knob raised), else read from global memory.
  *
  * gp_set_controller validates the table, uploads it synchronously and zeroes every node; thr_host = NULL removes the
  * controller. The nodes (uint8 [B], handle state) persist across calls; gp_reset zeroes them; gp_step / gp_rollout
@@ -344,7 +387,7 @@ int gp_controller_scores(gp_env* env, double* out, int cap_rows, int clear);
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
- * mask, elapsed. CARFLAG: s f32[B,3]
+ * mask, elapsed. HEAVENHELL: agent cell, heaven side (0 left, 1 right), elapsed. CARFLAG: s f32[B,3]
  * (position, velocity, direction), elapsed i32[B], heavens f32[B] (+-1), priests f32[B] (+-0.5; set takes
  * both by sign).
  * TAXI packs n_dropoffs into 4 bits: gp_set_state clamps it to [0, 15] and a goal move from 15 leaves it at 15
@@ -392,7 +435,7 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * "fused_tile_envs", "philox_step" (GP_RNG_PHILOX: the counter's step index that the next reset / step draws
  * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
  * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE, ANTTAG: always 0); ROCKSAMPLE,
- * ANTTAG and TAXI answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
+ * ANTTAG, TAXI and HEAVENHELL answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
  * rollout, 0 = no controller). GRID also: "controller_population" (P of the installed population, 0 = none),
  * "controller_group_envs" (its G), "controller_group_multiple" (1024: what G must be a multiple of); with a population
  * "controller_nodes" and "controller_lds" answer for one controller's table. Unknown keys return
@@ -445,10 +488,10 @@ int gp_profile_read_resolver(gp_env* env, double* total_ms, int64_t* n_launches)
  *   generic philox rollout even where a compile-time-specialised one exists), "no_wgrid" (GRID numpy mode: 1 =
  *   never the windowed kernel csrc/wgrid.hip), "wg_halo" (its window halo: 256 or 512 draws), "wg_bias" (added
  *   to its predicted reset count: forces window regenerations), "wg_tmode" (its timing-study variants, TM_* in
- *   csrc/wgrid.hip; results invalid for some), "ctrl_lds_max" (GRID and TAXI closed-loop rollouts, read by
+ *   csrc/wgrid.hip; results invalid for some), "ctrl_lds_max" (GRID, TAXI and HEAVENHELL closed-loop rollouts, read by
  *   gp_set_controller instead: the controller table is staged in LDS when the env's tables plus the table take at
  *   most this many bytes of LDS per block, at most 60 KB; 0 = always read from global memory, -1 = the default,
- *   32 KB), "persist_bpc" (TAXI / CROOMS / ANTTAG / ROCKSAMPLE persistent rollouts: blocks per CU, 0 = every
+ *   32 KB), "persist_bpc" (TAXI / CROOMS / ANTTAG / ROCKSAMPLE / HEAVENHELL persistent rollouts: blocks per CU, 0 = every
  *   resident block; TAXI keeps the value it was created with for its closed-loop grid too).
  *   gp_debug_reset restores the defaults. Unknown key: GP_E_INVALID. */
 int gp_debug_set(const char* key, int64_t value);
