@@ -28,6 +28,7 @@
 #include <cstring>
 #include <vector>
 
+#include "gp_ctrl.h"
 #include "gp_internal.h"
 #include "gp_libm.h"
 #include "ziggurat_tables.h"
@@ -676,6 +677,161 @@ __global__ __launch_bounds__(TPB, GP_CR_WAVES) void crooms_rollout(CrDev p, int 
       if (cr_velocity<SPEC>(p)) { p.vy[env] = vy[i]; p.vx[env] = vx[i]; }
       if (!cr_goal_fixed<SPEC>(p)) p.goal[env] = g[i];
       p.el[env] = el[i];
+    }
+  }
+  cr_metrics(p, rsum, eps, lens, nst);
+}
+
+// ---- the closed-loop rollout kernel (gp_rollout_controller; semantics in include/gym_po_amd.h) ----
+// The scalar obs of a state, as a value: the GP_OBS_HANSEN / GP_OBS_TABLE branches of write_obs restated (the
+// controller conditions on it from registers; tests/test_crooms_controller_gpu.py holds the two equal).
+template <int OK>
+__device__ __forceinline__ int32_t cr_scalar_obs(const CrDev& p, const uint8_t* lds, double ay, double ax, uint32_t g) {
+  static_assert(OK == GP_OBS_HANSEN || OK == GP_OBS_TABLE, "the scalar obs kinds");
+  const double gyc = (double)(int16_t)(g & 0xFFFF) + 0.5, gxc = (double)(int16_t)(g >> 16) + 0.5;
+  const int ac = max(cell_of(p, ay, ax), 0);
+  const int gc = cell_of(p, gyc, gxc);
+  if constexpr (OK == GP_OBS_HANSEN) {
+    const int32_t* doff = tab<int32_t>(lds, p.off_doff);
+    int mult = 1;
+    if (gc >= 0) {
+      const int diff = gc - ac;
+      for (int i = p.obs_dirs - 1; i >= 0; --i)
+        if (diff == doff[i]) mult = i + 1;
+    }
+    return (int32_t)tab<uint32_t>(lds, p.off_hbase)[ac] * mult;
+  } else {
+    int32_t v = tab<int32_t>(lds, p.off_t1)[ac];
+    if (p.has_t2) v += tab<int32_t>(lds, p.off_t2)[max(gc, 0)];
+    return v;
+  }
+}
+
+// Minimum waves per SIMD of the closed-loop kernel, from the gfx950 resource report: at 5 (a cap of 96
+// VGPRs) every instance spills 2 VGPRs into 12 B of scratch; at 4 it takes 98-100 VGPRs and no scratch.
+#ifndef GP_CR_CTRL_WAVES
+#define GP_CR_CTRL_WAVES 4
+#endif
+
+// K steps of every env, each action drawn by the installed controller (gp_ctrl.h) from the scalar obs of the state
+// the env is in and the env's node. crooms_rollout's geometry and inner step (crooms_env_step<false>); OK is
+// GP_OBS_HANSEN or GP_OBS_TABLE. CL: the controller table is staged in the dynamic LDS behind the env's tables
+// (c.lds_off = p.tab_bytes); otherwise its rows are read from global memory. A = 4 / 8, so a row holds exactly
+// L = A M entries: whole 16-B quads, no padding. Every output pointer may be null (not stored; block-uniform
+// branches). The controller's block always has 10 rounds, whatever CR_PHILOX_ROUNDS the env draws are built with.
+template <int OK, bool CL>
+__global__ __launch_bounds__(TPB, GP_CR_CTRL_WAVES) void crooms_rollout_ctrl(
+    CrDev p, CtrlDev c, int K, uint64_t step0, int32_t* __restrict__ obs, int32_t* __restrict__ aout,
+    uint8_t* __restrict__ nodes, float* __restrict__ rew, uint8_t* __restrict__ term, uint8_t* __restrict__ trunc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  stage_tables(p, lds);
+  if constexpr (CL) {
+    const uint4* src = (const uint4*)c.thr;
+    uint4* dst = (uint4*)(lds + c.lds_off);
+    for (int i = threadIdx.x; i < c.bytes / 16; i += TPB) dst[i] = src[i];
+  }
+  __syncthreads();
+  // the controller's fields as values, read before any branch (no selecting between fields of the by-value struct)
+  const uint32_t* cthr = CL ? reinterpret_cast<const uint32_t*>(lds + c.lds_off) : c.thr;
+  uint8_t* const cnode = c.node;
+  const int cM = c.M, cL = c.L;
+  const uint32_t cNobs = (uint32_t)c.n_obs, cInv = c.inv_m;
+  float rsum = 0.f;
+  uint32_t eps = 0, lens = 0, nst = 0;
+  for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
+    const int env0 = tile * EPB + threadIdx.x * EPT;
+    const bool both = env0 + EPT - 1 < p.B;
+    double ay[EPT], ax[EPT], vy[EPT], vx[EPT];
+    uint32_t g[EPT];
+    int32_t el[EPT], ob[EPT];
+    uint32_t nd[EPT];
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) {
+      const int env = env0 + i;
+      const bool live = env < p.B;
+      ay[i] = live ? p.ay[env] : 0.5;
+      ax[i] = live ? p.ax[env] : 0.5;
+      vy[i] = (live && p.use_velocity) ? p.vy[env] : 0.0;
+      vx[i] = (live && p.use_velocity) ? p.vx[env] : 0.0;
+      g[i] = live ? (p.goal_fixed ? ((uint32_t)(p.goal_y & 0xFFFF) | ((uint32_t)(p.goal_x & 0xFFFF) << 16))
+                                  : p.goal[env])
+                  : 0u;
+      el[i] = live ? p.el[env] : 0;
+      nd[i] = live ? (uint32_t)cnode[env] : 0u;
+      if (nd[i] >= (uint32_t)cM) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
+        if (live) atomicOr(p.derr, GP_DERR_CTRL);
+        nd[i] = (uint32_t)cM - 1u;
+      }
+      ob[i] = cr_scalar_obs<OK>(p, lds, ay[i], ax[i], g[i]);
+    }
+    for (int k = 0; k < K; ++k) {
+      const size_t off = (size_t)k * p.B;
+      const uint64_t stp = step0 + (uint64_t)k;
+      const bool full = both && (off & 1) == 0;  // pair-aligned 8-B / 2-B stores
+      int32_t a[EPT];
+      uint32_t jj[EPT];
+      uint8_t n2[EPT];
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) {
+        const int env = env0 + i;
+        const bool live = env < p.B;
+        const uint32_t y =
+            live ? philox4x32_10((uint32_t)env, (uint32_t)stp, (uint32_t)(stp >> 32), CTRL_TAG, p.key0, p.key1).x[0] >> 1
+                 : 0u;
+        uint32_t o = (uint32_t)ob[i];
+        if (o >= cNobs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
+          if (live) atomicOr(p.derr, GP_DERR_CTRL);
+          o = cNobs - 1u;
+        }
+        const uint32_t* row = cthr + ((size_t)nd[i] * (size_t)cNobs + o) * (size_t)cL;
+        jj[i] = min(ctrl_search(row, cL, y), (uint32_t)cL - 1u);  // (< L by the row's last entry, 2^31 > y)
+        a[i] = (int32_t)((jj[i] * cInv) >> 16);                   // j / M
+        n2[i] = (uint8_t)nd[i];
+      }
+      float r[EPT];
+      uint8_t tm[EPT], tr[EPT];
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) {
+        const int env = env0 + i;
+        const bool live = env < p.B;
+        const StepOut o = crooms_env_step<false>(p, lds, env, live, stp, 0.0, 0.0, a[i], ay[i], ax[i], vy[i], vx[i],
+                                                 g[i], el[i], rsum, eps, lens);
+        r[i] = o.rew;
+        tm[i] = o.term;
+        tr[i] = o.trunc;
+        nst += live ? 1u : 0u;
+        ob[i] = cr_scalar_obs<OK>(p, lds, ay[i], ax[i], g[i]);
+        nd[i] = (o.term | o.trunc) ? 0u : jj[i] - (uint32_t)a[i] * (uint32_t)cM;  // j % M; episode end: node 0
+      }
+      if (full) {
+        if (aout) *reinterpret_cast<int2*>(aout + off + env0) = make_int2(a[0], a[1]);
+        if (nodes) *reinterpret_cast<uint16_t*>(nodes + off + env0) = (uint16_t)(n2[0] | (n2[1] << 8));
+        if (rew) *reinterpret_cast<float2*>(rew + off + env0) = make_float2(r[0], r[1]);
+        if (term) *reinterpret_cast<uint16_t*>(term + off + env0) = (uint16_t)(tm[0] | (tm[1] << 8));
+        if (trunc) *reinterpret_cast<uint16_t*>(trunc + off + env0) = (uint16_t)(tr[0] | (tr[1] << 8));
+        if (obs) *reinterpret_cast<int2*>(obs + off + env0) = make_int2(ob[0], ob[1]);
+      } else {
+        for (int i = 0; i < EPT; ++i)
+          if (env0 + i < p.B) {
+            if (aout) aout[off + env0 + i] = a[i];
+            if (nodes) nodes[off + env0 + i] = n2[i];
+            if (rew) rew[off + env0 + i] = r[i];
+            if (term) term[off + env0 + i] = tm[i];
+            if (trunc) trunc[off + env0 + i] = tr[i];
+            if (obs) obs[off + env0 + i] = ob[i];
+          }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) {
+      const int env = env0 + i;
+      if (env >= p.B) continue;
+      p.ay[env] = ay[i];
+      p.ax[env] = ax[i];
+      if (p.use_velocity) { p.vy[env] = vy[i]; p.vx[env] = vx[i]; }
+      if (!p.goal_fixed) p.goal[env] = g[i];
+      p.el[env] = el[i];
+      cnode[env] = (uint8_t)nd[i];
     }
   }
   cr_metrics(p, rsum, eps, lens, nst);
@@ -2344,6 +2500,30 @@ struct CRoomsBackend : EnvBackend {
   std::vector<int32_t> valid_h;
   DevBuf b_tabs, b_ay, b_ax, b_vy, b_vx, b_goal, b_el, b_slot;
   DevErr derr;
+  // closed-loop rollouts (gp_set_controller; philox mode, a scalar obs, discrete actions)
+  CtrlDev ctrl{};  // M == 0: no controller installed
+  int grid_ctrl = 1, cus = 1;
+  size_t lds_ctrl = 0;  // dynamic LDS of the closed-loop launches
+  DevBuf b_cthr, b_cnode;
+  int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
+  int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
+                         hipStream_t s) override;
+  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
+    if (!ctrl.M) {
+      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
+      return GP_E_STATE;
+    }
+    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
+    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
+    return GP_OK;
+  }
+  int query(const char* key, int64_t* v) const override {
+    if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
+    else return EnvBackend::query(key, v);
+    return GP_OK;
+  }
   // exact (numpy-stream) mode
   DevBuf x_rng, x_wj, x_noise, x_wall, x_dense, x_u, x_gi, x_ai, x_rank;
   CrExact xd{};
@@ -2625,6 +2805,7 @@ struct CRoomsBackend : EnvBackend {
   }
   int reset(void* obs, hipStream_t s) override {
     GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(CrSlot) * grid, s));
+    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
     if (rng_mode == GP_RNG_REPLAY && ((!d.goal_fixed && !rp_goal) || (!d.agent_fixed && !rp_agent))) {
       gp_set_error("crooms replay reset needs goal/agent index draws (gp_set_replay i0/i1)");
       return GP_E_STATE;
@@ -2989,7 +3170,9 @@ int CRoomsBackend::build(const gp_crooms_config* cfg) {
   GP_HIP_CHECK(hipGetDeviceProperties(&prop, device));
   int occ = 0;
   GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout<GP_OBS_F32, false>, TPB, d.tab_bytes));
-  grid = persistent_grid(d.ntiles, prop.multiProcessorCount, occ);
+  cus = prop.multiProcessorCount;
+  grid = persistent_grid(d.ntiles, cus, occ);
+  grid_ctrl = grid;
   persist_grid = grid;
   persist_occ = occ;
   if ((e = b_slot.alloc(sizeof(CrSlot) * grid))) return e;
@@ -3000,6 +3183,111 @@ int CRoomsBackend::build(const gp_crooms_config* cfg) {
   xg_split = gp_debug_knobs().disable_fused != 0;
   xg_graph_mode = gp_xg_graph_knob;
   if (rng_mode == GP_RNG_NUMPY && (e = x_alloc())) return e;
+  return GP_OK;
+}
+
+// Closed-loop rollouts need the philox draws, a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE) and discrete actions.
+// thr_host rows hold L = A M entries (A = 4 or 8, M <= 8: L <= 64, up to which j / M by inv_m is exact): whole 16-B
+// quads, uploaded as they are. The table is staged in LDS behind the env's tables when both fit CTRL_LDS_BUDGET (knob
+// ctrl_lds_max, at most 60 KB: with the 64 B of static LDS a launch stays below 64 KB); the closed-loop grid is sized
+// from the kernel's occupancy at that dynamic-LDS size and never exceeds the open loop's (one set of metric slots).
+int CRoomsBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
+  if (rng_mode != GP_RNG_PHILOX) {
+    gp_set_error("crooms: controllers need rng_mode philox (%s mode has no counter-based draw for the controller)",
+                 rng_mode == GP_RNG_NUMPY ? "numpy" : "replay");
+    return GP_E_UNSUPPORTED;
+  }
+  if (d.action_kind == 0) {
+    gp_set_error("crooms: controllers need action_type cardinal or ordinal (yx has no discrete action space)");
+    return GP_E_UNSUPPORTED;
+  }
+  if (d.obs_kind != GP_OBS_HANSEN && d.obs_kind != GP_OBS_TABLE) {
+    gp_set_error("crooms: controllers need a scalar obs (hansen, hansen8, mdp, mdp_goal, room, room_goal), not the "
+                 "vector, window or continuous obs kind %d", d.obs_kind);
+    return GP_E_UNSUPPORTED;
+  }
+  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
+  if (!thr_host) {
+    ctrl = CtrlDev{};
+    int e;
+    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
+    return GP_OK;
+  }
+  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
+    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
+    return GP_E_INVALID;
+  }
+  const int L = d.nact * n_nodes;
+  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)L;
+  if (n > ((size_t)1 << 28)) {
+    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
+    return GP_E_INVALID;
+  }
+  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L)) return e;
+  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
+  std::vector<uint32_t> host(thr_host, thr_host + n);
+  int e;
+  if ((e = b_cthr.upload(host)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
+  CtrlDev c{};
+  c.thr = b_cthr.as<uint32_t>();
+  c.node = b_cnode.as<uint8_t>();
+  c.M = n_nodes;
+  c.n_obs = n_obs;
+  c.L = L;
+  c.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
+  c.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
+  const int knob = gp_debug_knobs().ctrl_lds_max;
+  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
+  const bool staged = (size_t)d.tab_bytes + n * sizeof(uint32_t) <= budget;
+  c.lds_off = staged ? d.tab_bytes : -1;
+  lds_ctrl = (size_t)d.tab_bytes + (staged ? n * sizeof(uint32_t) : 0);
+  int occ = 0;
+  const bool hansen = d.obs_kind == GP_OBS_HANSEN;
+  if (hansen && staged) {
+    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_HANSEN, true>, TPB, lds_ctrl));
+  } else if (hansen) {
+    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_HANSEN, false>, TPB, lds_ctrl));
+  } else if (staged) {
+    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_TABLE, true>, TPB, lds_ctrl));
+  } else {
+    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_TABLE, false>, TPB, lds_ctrl));
+  }
+  grid_ctrl = std::min(persistent_grid(d.ntiles, cus, occ), grid);
+  ctrl = c;
+  return GP_OK;
+}
+
+int CRoomsBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term,
+                                      uint8_t* trunc, hipStream_t s) {
+  if (!has_reset || !ctrl.M) {
+    gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
+                                                                      "(gp_set_controller)");
+    return GP_E_STATE;
+  }
+  // the kernel's pair stores: 8 B of 4-byte elements, 2 B of flags (null: not stored)
+  auto al = [](const void* x, uintptr_t m) { return ((uintptr_t)x & (m - 1)) == 0; };
+  if (!al(act, 8) || !al(obs, 8) || !al(rew, 8) || !al(nodes, 2) || !al(term, 2) || !al(trunc, 2)) {
+    gp_set_error("crooms: misaligned obs / action / reward (8 B) or node / flag (2 B) buffer");
+    return GP_E_INVALID;
+  }
+  const CrDev dd = dev_for_launch();
+  const bool hansen = d.obs_kind == GP_OBS_HANSEN, staged = ctrl.lds_off >= 0;
+  timer.begin(s);
+  if (hansen && staged)
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_HANSEN, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+                       philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+  else if (hansen)
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_HANSEN, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+                       philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+  else if (staged)
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_TABLE, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+                       philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+  else
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_TABLE, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+                       philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+  timer.end(s);
+  philox_step += (uint64_t)K;
+  GP_HIP_CHECK(hipGetLastError());
   return GP_OK;
 }
 

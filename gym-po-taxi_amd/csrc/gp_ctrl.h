@@ -1,5 +1,5 @@
 // gp_ctrl.h — the tabular finite-state controller of the closed-loop rollouts (gp_set_controller; semantics in
-// include/gym_po_amd.h), shared by the kinds that run it (grid.hip, rocksample.hip, anttag.hip, taxi.hip): the device view of an
+// include/gym_po_amd.h), shared by the kinds that run it (grid.hip, rocksample.hip, anttag.hip, taxi.hip, heavenhell.hip, crooms.hip): the device view of an
 // installed table, the threshold-row search and the host-side validation of a table. Per env-step one Philox block tagged
 // CTRL_TAG picks j = action * M + next_node from the threshold row of (node, obs).
 #pragma once
@@ -7,10 +7,10 @@
 #include "gp_common.h"
 
 // the env draws carry 0x67706f21 (grid) / 0x726f636b (rocksample) / 0x616e7431 (anttag) / 0x74617869 (taxi) /
-// 0x6868656c (heavenhell)
+// 0x6868656c (heavenhell) / 0x63726f6f and 0x6d733121 (crooms)
 constexpr uint32_t CTRL_TAG = 0x67706f63u;
 // Largest dynamic LDS per block (env tables + controller table) up to which the kinds that stage the table in LDS
-// (grid.hip, taxi.hip) do so by default; the knob ctrl_lds_max overrides it, up to 60 KB.
+// (grid.hip, taxi.hip, heavenhell.hip, crooms.hip) do so by default; the knob ctrl_lds_max overrides it, up to 60 KB.
 constexpr int CTRL_LDS_BUDGET = 32 * 1024;
 struct CtrlDev {
   const uint32_t* thr;  // [M][n_obs][L]: nondecreasing rows, entries <= 2^31, last == 2^31 (validated on upload)

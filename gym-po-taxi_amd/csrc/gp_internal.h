@@ -43,7 +43,7 @@ struct GpDebugKnobs {
   int wg_block_envs = 0;    // GRID windowed kernel: the smallest envs per block to use (0 = the smallest that fits)
   int wg_fill_simd = 0;     // GRID windowed kernel: per-SIMD window-row deltas, 4 signed nibbles (0 = WG_FILL_SIMD)
   int64_t wg_fill_wave = 0; // GRID windowed kernel: per-wave deltas on top, 8 signed nibbles (wave 0 lowest)
-  int ctrl_lds_max = -1;    // GRID / TAXI / HEAVENHELL closed-loop rollouts: dynamic LDS bytes per block up to which the controller table is staged in LDS (0 = never; -1 = gp_ctrl.h CTRL_LDS_BUDGET; at most 60 KB); read by gp_set_controller
+  int ctrl_lds_max = -1;    // GRID / TAXI / HEAVENHELL / CROOMS closed-loop rollouts: dynamic LDS bytes per block up to which the controller table is staged in LDS (0 = never; -1 = gp_ctrl.h CTRL_LDS_BUDGET; at most 60 KB); read by gp_set_controller
   int persist_bpc = 0;      // TAXI / CROOMS / ANT-TAG / ROCKSAMPLE / HEAVENHELL streaming rollouts: blocks per CU (0 = every resident block, persistent_grid); TAXI keeps the value of gp_create for its closed-loop grid (set_controller)
 };
 const GpDebugKnobs& gp_debug_knobs();
@@ -102,7 +102,8 @@ struct EnvBackend {
     return GP_E_UNSUPPORTED;
   }
   // Closed-loop rollouts (gp_set_controller / gp_rollout_controller / gp_controller_nodes): GRID in philox mode,
-  // ROCKSAMPLE, ANTTAG with the index obs in philox mode, TAXI with the Hansen obs in philox mode, HEAVENHELL.
+  // ROCKSAMPLE, ANTTAG with the index obs in philox mode, TAXI with the Hansen obs in philox mode, HEAVENHELL,
+  // CROOMS with a scalar obs and discrete actions in philox mode.
   virtual int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
     gp_set_error("controllers are not supported by this env kind");
     return GP_E_UNSUPPORTED;

@@ -291,8 +291,10 @@ class NativeVecEnv:
         """Install the tabular controller of the closed-loop rollouts (FourRooms / ROOMS with a scalar obs in
         rng_mode='philox', RockSample, where A * M may not exceed 64, AntTagGridEnv with obs_type='index' in
         rng_mode='philox', TaxiVecEnv with hansen_obs=True in rng_mode='philox', scalar or one-hot: the table is
-        indexed by the scalar Hansen obs either way, and HeavenHellGridEnv with either obs_type), or remove it when
-        both arguments are None. `probs`: float [M, n_obs, A, M], the joint probability of (action, next node) given
+        indexed by the scalar Hansen obs either way, HeavenHellGridEnv with either obs_type, and CRoomsEnv with
+        action_type 'cardinal' (A = 4) or 'ordinal' (A = 8) and a scalar obs_type (hansen, hansen8, mdp, mdp_goal,
+        room, room_goal) in rng_mode='philox'; its 'yx' actions, vector / grid obs and numpy / replay modes raise
+        GymPoError naming the condition), or remove it when both arguments are None. `probs`: float [M, n_obs, A, M], the joint probability of (action, next node) given
         (node, obs), or [n_obs, A] for a memoryless policy; lowered by `controller.controller_thresholds`. `thresholds`: that uint32
         [M, n_obs, A * M] table itself. n_obs is `single_observation_space.n` (a one-hot Taxi's row width `no`), A the
         action count, M <= 8. Every env's node becomes 0. Raises GymPoError for a table that does not fit the env or
@@ -326,7 +328,7 @@ class NativeVecEnv:
 
     def set_controller_population(self, probs=None, thresholds=None, group_envs=None, gamma=1.0):
         """Install P controllers side by side (FourRooms / ROOMS with a scalar obs in rng_mode='philox'; every other
-        env, HeavenHellGridEnv included, raises GymPoError), or remove
+        env, HeavenHellGridEnv and CRoomsEnv included, raises GymPoError), or remove
         whatever controller is installed when `probs` and `thresholds` are both None. Env e is driven by controller
         e // group_envs; `controller_scores()` then gives one score row per controller, its discounted return under
         `gamma` (float32, in (0, 1]) included. `probs`: float [P, M, n_obs, A, M], lowered by
@@ -398,7 +400,8 @@ class NativeVecEnv:
         of `store` are not written at all (store=() is a pure policy evaluation, read through metrics()). `out`
         may supply preallocated buffers as a dict by name (term / trunc as uint8), checked for shape, dtype, device
         and contiguity (ValueError otherwise). Feeding `actions` to rollout() on a twin env of the same seed
-        reproduces obs, rew, term and trunc bit for bit."""
+        reproduces obs, rew, term and trunc bit for bit (CRoomsEnv: the float64 positions and velocities of
+        get_state() too)."""
         torch = _torch()
         fn = self._ctrl_fn("gp_rollout_controller")
         K = int(K)
@@ -440,7 +443,8 @@ class NativeVecEnv:
     @property
     def controller_nodes(self):
         """The controller node of every env, uint8 [B] on the device (a copy). Assigning an array-like [B] replaces
-        them (values below the controller's node count); reset() and set_controller() zero them."""
+        them (values below the controller's node count); reset() and set_controller() zero them; step(), rollout()
+        and CRoomsEnv.set_state() leave them alone."""
         torch = _torch()
         t = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
         check(self._ctrl_fn("gp_controller_nodes")(self._handle, ctypes.c_void_p(t.data_ptr()), None, self._stream()),

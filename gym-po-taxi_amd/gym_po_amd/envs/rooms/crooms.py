@@ -17,6 +17,12 @@ Philox-mode normals are Box-Muller on float32 hardware log2 / sqrt / sin / cos (
 reaches 8.57 sigma), scaled in float64: the noise has float32 precision (~1e-7 relative) while the state is
 float64 -- the reference's law, not its values (csrc/crooms.hip box_muller_pair).
 
+Closed-loop rollouts (`set_controller` / `rollout_controller` / `controller_nodes`, core.py): with
+action_type "cardinal" or "ordinal", a scalar obs_type (hansen, hansen8, mdp, mdp_goal, room, room_goal) and
+rng_mode "philox", a tabular finite-state controller picks every action on the device from the obs of the state the
+env is in, K steps per launch (csrc/crooms.hip crooms_rollout_ctrl). Controller populations are not
+available here.
+
 Extra keyword arguments beyond the reference: `device`, `rng_mode`, `dtype` (torch.float32 (default)
 or torch.float64 for the continuous actions and observations).
 """

@@ -288,8 +288,9 @@ void gp_plan_destroy(gp_plan* plan);
 /* ---- closed-loop rollouts: a tabular finite-state controller evaluated inside the rollout kernel ----
  * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), ROCKSAMPLE (either obs), ANTTAG with the
  * index obs (obs_index = 1) in GP_RNG_PHILOX, TAXI with the Hansen obs (GP_OBS_HANSEN, one_hot 0 or 1) in
- * GP_RNG_PHILOX, and HEAVENHELL (any obs base); every other kind, rng mode and obs kind: GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host,
- * one step() per action.)
+ * GP_RNG_PHILOX, HEAVENHELL (any obs base), and CROOMS in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN /
+ * GP_OBS_TABLE) and discrete actions (action_kind 4 or 8); every other kind, rng mode and obs kind:
+ * GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host, one step() per action.)
  *
  * The controller has M = n_nodes nodes (1..8; M = 1 is a memoryless policy obs -> action distribution). With A the
  * env's action count and L = A * M, thr_host is uint32 [M][n_obs][L] (host memory): row (node, obs) holds the
@@ -325,10 +326,22 @@ void gp_plan_destroy(gp_plan* plan);
  * entries, whole 16-B quads: nothing is padded. n_obs is the caller's (the obs space has obs_base_n * 3 values). The
  * table is staged in LDS behind the env's tables when both fit the "ctrl_lds_max" budget (the 48-value Hansen obs:
  * M = 2 is 3 KB, M = 5 is 18.75 KB; M = 8, 48 KB, needs the knob raised), else read from global memory.
+ * CROOMS: GP_RNG_PHILOX, obs_kind GP_OBS_HANSEN or GP_OBS_TABLE, action_kind 4 (cardinal) or 8 (ordinal); GP_RNG_NUMPY,
+ * GP_RNG_REPLAY, action_kind 0 (yx: no discrete action space) and the vector, window and continuous obs kinds (no
+ * scalar obs) are GP_E_UNSUPPORTED, the message saying which applies. use_velocity, a random or fixed goal, a fixed
+ * agent, cell_size, action_std, action_power and float32 / float64 I/O do not matter. The obs is computed from the
+ * float64 position and the goal in registers exactly as the obs plane's value is; the controller's block always has
+ * 10 Philox rounds; the env draws carry 0x63726f6f (noise) and 0x6d733121 (failure and reset draws). A = 4 or 8, so
+ * rows hold exactly L = A M <= 64 entries, whole 16-B quads: nothing is padded (A = 8 with M = 8 sits at the j / M
+ * multiply's limit). n_obs is the caller's (Hansen-4: 80 values, Hansen-8: 2,304, mdp: the valid cells, mdp_goal:
+ * their square). The table is staged in LDS behind the env's tables when both fit the "ctrl_lds_max" budget (layout
+ * "4": Hansen-4 with 4 actions and M = 1 is 1.25 KB; Hansen-8 with 8 actions is 72 KB at M = 1 and mdp_goal has
+ * 40,000 obs values: global memory). An obs the env computes outside [0, n_obs) (cell_size > 1 puts positions on
+ * wall cells, whose table value is -1, as in the reference) is clamped and flagged like any other.
  *
  * gp_set_controller validates the table, uploads it synchronously and zeroes every node; thr_host = NULL removes the
  * controller. The nodes (uint8 [B], handle state) persist across calls; gp_reset zeroes them; gp_step / gp_rollout
- * (and, TAXI, gp_set_state) leave them alone.
+ * (and, TAXI and CROOMS, gp_set_state) leave them alone.
  * gp_rollout_controller runs K steps in one launch. obs [K,B] int32, rew [K,B] float, term / trunc [K,B] uint8 as
  * gp_rollout; actions int32 [K,B]: the actions taken; nodes uint8 [K,B]: the node each action was chosen in. Every
  * output pointer may be NULL (not stored); with all of them NULL the call is a pure policy evaluation, read through
@@ -435,7 +448,7 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * "fused_tile_envs", "philox_step" (GP_RNG_PHILOX: the counter's step index that the next reset / step draws
  * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
  * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE, ANTTAG: always 0); ROCKSAMPLE,
- * ANTTAG, TAXI and HEAVENHELL answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
+ * ANTTAG, TAXI, HEAVENHELL and CROOMS answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
  * rollout, 0 = no controller). GRID also: "controller_population" (P of the installed population, 0 = none),
  * "controller_group_envs" (its G), "controller_group_multiple" (1024: what G must be a multiple of); with a population
  * "controller_nodes" and "controller_lds" answer for one controller's table. Unknown keys return
@@ -488,7 +501,7 @@ int gp_profile_read_resolver(gp_env* env, double* total_ms, int64_t* n_launches)
  *   generic philox rollout even where a compile-time-specialised one exists), "no_wgrid" (GRID numpy mode: 1 =
  *   never the windowed kernel csrc/wgrid.hip), "wg_halo" (its window halo: 256 or 512 draws), "wg_bias" (added
  *   to its predicted reset count: forces window regenerations), "wg_tmode" (its timing-study variants, TM_* in
- *   csrc/wgrid.hip; results invalid for some), "ctrl_lds_max" (GRID, TAXI and HEAVENHELL closed-loop rollouts, read by
+ *   csrc/wgrid.hip; results invalid for some), "ctrl_lds_max" (GRID, TAXI, HEAVENHELL and CROOMS closed-loop rollouts, read by
  *   gp_set_controller instead: the controller table is staged in LDS when the env's tables plus the table take at
  *   most this many bytes of LDS per block, at most 60 KB; 0 = always read from global memory, -1 = the default,
  *   32 KB), "persist_bpc" (TAXI / CROOMS / ANTTAG / ROCKSAMPLE / HEAVENHELL persistent rollouts: blocks per CU, 0 = every
