@@ -42,6 +42,9 @@ const char* gp_derr_text(uint32_t flags) {
   if (flags & GP_DERR_CTRL)
     strncat(buf, "a closed-loop rollout met an obs or node outside the controller table (the device clamped it); ",
             sizeof(buf) - strlen(buf) - 1);
+  if (flags & GP_DERR_STATS)
+    strncat(buf, "gp_controller_stats met a visit outside the table or a return-to-go of 2^31 or more, NaN included (the "
+                 "visit was skipped; the tables lack it); ", sizeof(buf) - strlen(buf) - 1);
   return buf;
 }
 
@@ -234,6 +237,7 @@ int gp_debug_set(const char* key, int64_t value) {
   else if (!strcmp(key, "xg_spb_min")) g_dbg.xg_spb_min = (int)value;
   else if (!strcmp(key, "persist_bpc")) g_dbg.persist_bpc = (int)value;
   else if (!strcmp(key, "ctrl_lds_max")) g_dbg.ctrl_lds_max = (int)value;
+  else if (!strcmp(key, "stats_lds_max")) g_dbg.stats_lds_max = (int)value;
   else if (!strcmp(key, "xg_graph")) gp_xg_graph_knob = (int)value;  // (crooms.hip: read at create)
   else {
     gp_set_error("gp_debug_set: unknown key '%s'", key);
@@ -471,6 +475,31 @@ int gp_set_controller_population(gp_env* env, int n_ctrl, int64_t group_envs, in
 int gp_controller_scores(gp_env* env, double* out, int cap_rows, int clear) {
   GP_REQUIRE_ENV();
   return env->be->controller_scores(out, cap_rows, clear);
+}
+
+int gp_controller_stats(gp_env* env, int K, const int32_t* obs0, const int32_t* obs, const int32_t* actions,
+                        const uint8_t* nodes, const uint8_t* next_nodes, const float* rew, const uint8_t* term,
+                        const uint8_t* trunc, const float* bootstrap, float gamma, int64_t* counts, int64_t* ret_q,
+                        void* stream) {
+  GP_REQUIRE_ENV();
+  CtrlShape c;
+  if (int e = env->be->controller_shape(&c)) return e;  // GP_E_UNSUPPORTED (the kind) or GP_E_STATE (nothing installed)
+  if (K < 0 || !counts || !ret_q ||
+      (K > 0 && (!obs0 || !obs || !actions || !nodes || !next_nodes || !rew || !term || !trunc))) {
+    gp_set_error("gp_controller_stats: bad arguments (K >= 0; only bootstrap may be null)");
+    return GP_E_INVALID;
+  }
+  if (!(gamma > 0.0f && gamma <= 1.0f)) {
+    gp_set_error("gp_controller_stats: gamma must be in (0, 1] (got %g)", (double)gamma);
+    return GP_E_INVALID;
+  }
+  if ((((uintptr_t)counts) | ((uintptr_t)ret_q)) & 7u) {
+    gp_set_error("gp_controller_stats: counts and ret_q must be 8-byte aligned");
+    return GP_E_INVALID;
+  }
+  if (K == 0) return GP_OK;
+  return ctrl_stats_launch(c, env->be->B, K, obs0, obs, actions, nodes, next_nodes, rew, term, trunc, bootstrap, gamma,
+                           counts, ret_q, &env->be->stats_path, (hipStream_t)stream);
 }
 
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream) {

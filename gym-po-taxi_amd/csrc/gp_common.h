@@ -144,6 +144,8 @@ GP_HD uint32_t st_count(uint64_t s) { return (uint32_t)s; }
                             // inversion did not end, neither of which the device walker restates
 #define GP_DERR_CTRL 32u    // closed-loop rollout: an obs outside the controller table's n_obs, or a node >= its
                             // node count (set through gp_controller_nodes): the device clamped it
+#define GP_DERR_STATS 64u   // gp_controller_stats: a visit whose node, obs, action or next node lies outside the table,
+                            // or whose return-to-go is not below 2^31 in magnitude (NaN included): the visit was skipped
 // numpy indexing of an n-row table accepts a in [-n, n) (negatives wrap); anything else raises.
 __device__ __forceinline__ bool action_out_of_range(int a, int n) { return (uint32_t)(a + n) >= (uint32_t)(2 * n); }
 __device__ __forceinline__ void flag_bad_action(uint32_t* derr) { atomicOr(derr, GP_DERR_ACTION); }

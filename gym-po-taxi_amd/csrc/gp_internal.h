@@ -44,6 +44,7 @@ struct GpDebugKnobs {
   int wg_fill_simd = 0;     // GRID windowed kernel: per-SIMD window-row deltas, 4 signed nibbles (0 = WG_FILL_SIMD)
   int64_t wg_fill_wave = 0; // GRID windowed kernel: per-wave deltas on top, 8 signed nibbles (wave 0 lowest)
   int ctrl_lds_max = -1;    // GRID / TAXI / HEAVENHELL / CROOMS closed-loop rollouts: dynamic LDS bytes per block up to which the controller table is staged in LDS (0 = never; -1 = gp_ctrl.h CTRL_LDS_BUDGET; at most 60 KB); read by gp_set_controller
+  int stats_lds_max = -1;   // gp_controller_stats: LDS bytes per block up to which one controller's tables are accumulated in a block-private LDS histogram (0 = never: global atomics; -1 = ctrl_stats.hip STATS_LDS_BUDGET; at most 60 KB); read at every call
   int persist_bpc = 0;      // TAXI / CROOMS / ANT-TAG / ROCKSAMPLE / HEAVENHELL streaming rollouts: blocks per CU (0 = every resident block, persistent_grid); TAXI keeps the value of gp_create for its closed-loop grid (set_controller)
 };
 const GpDebugKnobs& gp_debug_knobs();
@@ -60,6 +61,15 @@ inline int persistent_grid(int ntiles, int cus, int occ) {
   const int g = cus * bpc;
   return ntiles < g ? (ntiles > 0 ? ntiles : 1) : g;
 }
+
+// What gp_controller_stats (ctrl_stats.hip) needs to know of a handle: the shape of the installed controller or
+// population and the handle's device error word. Filled by EnvBackend::controller_shape.
+struct CtrlShape {
+  int M = 0, n_obs = 0, A = 0;  // nodes and obs values of the installed table, actions of the env
+  int P = 1;                    // controllers of an installed population (1: a single controller)
+  int64_t G = 0;                // envs per group of a population, a multiple of 1024 (0: a single controller)
+  uint32_t* derr = nullptr;     // device error word (GP_DERR_*)
+};
 
 // Per-kind backend interface; gp_env owns one.
 // hipEvent pairs around the step-kernel launches (gp_set_profiling / gp_profile_read).
@@ -127,6 +137,21 @@ struct EnvBackend {
     gp_set_error("controller populations are not supported by this env kind (GRID only)");
     return GP_E_UNSUPPORTED;
   }
+  // Controller statistics (gp_controller_stats): the six kinds with closed-loop rollouts answer the shape of what is
+  // installed (GP_E_STATE: nothing is); the call itself is kind-independent (ctrl_stats.hip).
+  virtual int controller_shape(CtrlShape* out) const {
+    gp_set_error("controllers are not supported by this env kind");
+    return GP_E_UNSUPPORTED;
+  }
+  int ctrl_shape_of(int M, int n_obs, int A, int P, int64_t G, uint32_t* derr, CtrlShape* out) const {
+    if (!M) {
+      gp_set_error("gp_controller_stats without a controller (gp_set_controller / gp_set_controller_population)");
+      return GP_E_STATE;
+    }
+    *out = CtrlShape{M, n_obs, A, P > 0 ? P : 1, P > 0 ? G : 0, derr};
+    return GP_OK;
+  }
+  int stats_path = -1;  // the last gp_controller_stats launch: 1 = LDS histogram, 0 = global atomics (gp_query "stats_lds")
   virtual int valid_cells(int which, int32_t* out, int cap) const { return 0; }
   virtual int metrics(double out[4]) = 0;
   // Syncs and reports device-side failures of earlier launches (GP_E_DEVICE); kinds without
@@ -138,7 +163,12 @@ struct EnvBackend {
     else if (!strcmp(key, "rng_mode")) *v = rng_mode;
     else if (!strcmp(key, "persist_blocks")) *v = persist_grid;
     else if (!strcmp(key, "persist_occupancy")) *v = persist_occ;
-    else {
+    else if (!strcmp(key, "stats_lds")) *v = stats_path;
+    else if (!strcmp(key, "controller_n_obs") || !strcmp(key, "controller_actions")) {
+      CtrlShape c;
+      if (int e = controller_shape(&c)) return e;
+      *v = key[11] == 'n' ? c.n_obs : c.A;
+    } else {
       gp_set_error("gp_query: unknown key '%s'", key);
       return GP_E_INVALID;
     }
@@ -162,6 +192,13 @@ struct EnvBackend {
   size_t obs_elem_size() const { return obs_dtype == GP_DTYPE_U8 ? 1 : (obs_dtype == GP_DTYPE_F64 ? 8 : 4); }
   virtual size_t rollout_action_bytes_per_env() const { return 4; }
 };
+
+// ctrl_stats.hip: the one launch of gp_controller_stats (K >= 1, arguments validated by the caller); *lds_path receives
+// 1 if it took the LDS histogram, 0 if global atomics.
+int ctrl_stats_launch(const CtrlShape& c, int64_t B, int K, const int32_t* obs0, const int32_t* obs,
+                      const int32_t* actions, const uint8_t* nodes, const uint8_t* next_nodes, const float* rew,
+                      const uint8_t* term, const uint8_t* trunc, const float* bootstrap, float gamma, int64_t* counts,
+                      int64_t* ret_q, int* lds_path, hipStream_t s);
 
 std::unique_ptr<EnvBackend> make_grid_backend(const gp_grid_config* cfg, int64_t B, int device, int rng_mode, int* err);
 std::unique_ptr<EnvBackend> make_taxi_backend(const gp_taxi_config* cfg, int64_t B, int device, int rng_mode, int* err);

@@ -3098,6 +3098,7 @@ struct GridBackend : EnvBackend {
   CtrlDev ctrl{};            // M == 0: no controller installed
   DevBuf b_cthr, b_cnode;
   int controller_unsupported(const char* what) const;
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, d.nact, pop_P, pop_G, &d.ctl->err, out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override;

@@ -419,6 +419,7 @@ struct HeavenHellBackend : EnvBackend {
     has_reset = true;
     return GP_OK;
   }
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, NACT, 0, 0, derr.ptr(), out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override {

@@ -108,6 +108,8 @@ SIGNATURES = {
     "gp_set_controller_population": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                     ctypes.c_float, _vp]),
     "gp_controller_scores": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int]),
+    "gp_controller_stats": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           ctypes.c_float, _vp, _vp, _vp]),
     "gp_get_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_replay": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

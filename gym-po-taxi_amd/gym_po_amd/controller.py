@@ -45,6 +45,60 @@ def controller_thresholds(probs):
     return t.astype(np.uint32)
 
 
+STATS_SCALE_BITS = 20  # ret_q of NativeVecEnv.controller_statistics counts returns in units of 2^-20
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def stats_returns(ret_q):
+    """int64 fixed-point return sums `ret_q` of `NativeVecEnv.controller_statistics` -> float64 sums (x 2^-20; exact
+    below 2^53 units)."""
+    return _host(ret_q).astype(np.float64) * 2.0 ** -STATS_SCALE_BITS
+
+
+def q_estimate(counts, ret_q):
+    """The mean return-to-go per table cell [..., M, n_obs, A, M + 1] (the Monte Carlo estimate of the value of
+    making that choice), NaN where a cell was never visited."""
+    c = _host(counts).astype(np.float64)
+    s = stats_returns(ret_q)
+    return np.divide(s, c, out=np.full(s.shape, np.nan), where=c > 0)
+
+
+def policy_gradient(probs, counts, ret_q):
+    """The unnormalised likelihood-ratio gradient sum over visits of G * d log pi / d logits, with respect to the
+    per-row joint softmax logits z[n, o, a, n'] (pi[n, o] = softmax of z[n, o] over the A * M joint choices).
+
+    probs float [M, n_obs, A, M] (or [n_obs, A] for M = 1), counts / ret_q int64 [M, n_obs, A, M + 1] from
+    `NativeVecEnv.controller_statistics`; all three may carry a leading population axis P. With S =
+    stats_returns(ret_q), C = S[..., :M] (visits whose next node is known), E = S[..., M] (visits that ended the
+    episode, scored by the action marginal pi_a = sum over n' of pi), and sums over a row's (a, n'):
+
+        grad[n, o, a, n'] = C[n, o, a, n'] - pi[n, o, a, n'] * sum C[n, o]
+                            + E[n, o, a] * pi[n, o, a, n'] / pi_a[n, o, a] - pi[n, o, a, n'] * sum E[n, o]
+
+    the third term being 0 where pi_a is 0. Returns float64 shaped like probs. `counts` fixes the shape only (divide
+    by counts.sum() for a per-visit mean)."""
+    p = np.asarray(probs, dtype=np.float64)
+    s = stats_returns(ret_q)
+    flat = p.ndim == s.ndim - 2  # [n_obs, A] (or [P, n_obs, A]) for M = 1
+    if flat:
+        p = p[..., None, :, :, None]
+    if p.ndim not in (4, 5) or p.shape[-1] != p.shape[-4] or s.shape != p.shape[:-1] + (p.shape[-1] + 1,) \
+            or np.shape(_host(counts)) != s.shape:
+        raise ValueError(f"probs {np.shape(probs)} must be [(P,) M, n_obs, A, M] and counts / ret_q [(P,) M, n_obs, A, "
+                         f"M + 1], got {np.shape(_host(counts))} / {s.shape}")
+    M = p.shape[-1]
+    C, E = s[..., :M], s[..., M]
+    pa = p.sum(-1)
+    ratio = np.divide(p, pa[..., None], out=np.zeros_like(p), where=pa[..., None] > 0)
+    sum_c = C.sum((-1, -2))[..., None, None]
+    sum_e = E.sum(-1)[..., None, None]
+    g = C - p * sum_c + E[..., None] * ratio - p * sum_e
+    return g[..., 0, :, :, 0] if flat else g
+
+
 def population_thresholds(probs):
     """float probs [P, M, n_obs, A, M], P controllers of one shape -> uint32 thresholds [P, M, n_obs, A * M] for
     `NativeVecEnv.set_controller_population`: `controller_thresholds` applied to each controller. Raises ValueError

@@ -466,6 +466,92 @@ class NativeVecEnv:
             raise ValueError(f"controller_nodes: need {self.num_envs} values, got shape {tuple(t.shape)}")
         check(fn(self._handle, None, ctypes.c_void_p(t.data_ptr()), self._stream()), "gp_controller_nodes")
 
+    def _stats_plane(self, name, t, shape, dtypes, cast=None):
+        """A plane of controller_statistics as a contiguous device tensor: `dtypes` are accepted as they are (a view
+        at any storage offset included), `cast` = (kinds, dtype) converts those dtype kinds; ValueError otherwise."""
+        torch = _torch()
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(np.asarray(t))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"controller_statistics: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        if t.dtype not in dtypes:
+            if cast is None or not (t.dtype.is_floating_point or t.dtype in cast[0]):
+                raise ValueError(f"controller_statistics: {name} must be {' or '.join(map(str, dtypes))}, got {t.dtype}")
+            t = t.to(cast[1])
+        if t.dtype == torch.bool:
+            t = t.view(torch.uint8)
+        return t.to(self.device).contiguous()
+
+    def controller_statistics(self, planes, obs0, next_nodes=None, gamma=1.0, bootstrap=None, into=None):
+        """Visit counts and return-to-go sums per controller table cell over K stored closed-loop steps, accumulated
+        on the device in ONE launch as exact integers (bit-reproducible: no float atomics): the sufficient statistics
+        of a policy-gradient, Monte Carlo policy-iteration or EM step (`controller.q_estimate`, `policy_gradient`).
+
+        `planes`: the dict rollout_controller(K) returned, all six entries (obs, actions, nodes, rew, term, trunc).
+        obs must be a scalar [K, B] plane (a one-hot Taxi plane is a ValueError; other integer or float obs dtypes are
+        cast to int32). `obs0` [B]: the obs before the first of the K steps (what reset() or the previous rollout's
+        last obs row gave). `next_nodes` uint8 [B]: the controller nodes after the K-th step; None reads
+        `controller_nodes` NOW, which is correct only when called right after the rollout that wrote `planes`, before
+        any other closed-loop rollout, reset() or node assignment. `gamma`: float32 in (0, 1]. `bootstrap` float32 [B]
+        or None (0): the value after the K-th step. `into`: a dict {"counts", "ret_q"} of int64 device tensors to
+        accumulate into (the call adds); None makes fresh zeroed ones.
+
+        Returns {"counts", "ret_q"}: int64 [M, n_obs, A, M + 1] ([P, ...] with a population; env e belongs to
+        controller e // group_envs). The cell of step k is (nodes[k], the obs before it, actions[k], next node), the
+        next node being nodes[k + 1] (next_nodes after the last step), or column M when the step ended the episode
+        (terminated or truncated; the return stops there too). G_k = rew[k] + gamma * G_{k+1} in float32, two
+        roundings; ret_q sums rint(G_k * 2^20) (`controller.stats_returns` scales back). An entry overflows once the
+        sum of |G| over its visits reaches 2^43. A visit outside the table, or with |G| not below 2^31 (NaN included),
+        is skipped and flags the handle: check() raises until the next seed. Raises GymPoError without an installed
+        controller and on envs without closed-loop rollouts. Needs no reset(): only the planes are read."""
+        torch = _torch()
+        fn = self._ctrl_fn("gp_controller_stats")
+        # the shape of what is installed (first: its errors say that the kind has no controllers, or that none is set)
+        n_obs, A, M = (self.query(k) for k in ("controller_n_obs", "controller_actions", "controller_nodes"))
+        if not isinstance(planes, dict) or any(n not in planes for n in self._CTRL_OUTPUTS):
+            raise ValueError(f"controller_statistics: planes must be a dict with all of {self._CTRL_OUTPUTS}")
+        obs = planes["obs"]
+        if not isinstance(obs, torch.Tensor):
+            obs = torch.as_tensor(np.asarray(obs))
+        if obs.ndim != 2:
+            raise ValueError(f"controller_statistics: obs must be a scalar [K, B] plane, got shape {tuple(obs.shape)} "
+                             "(a one-hot obs plane is not supported: create the env with the scalar obs)")
+        K, B = int(obs.shape[0]), self.num_envs
+        ints = (torch.int64, torch.int16, torch.int8, torch.uint8)
+        lead = (K, B)
+        obs = self._stats_plane("obs", obs, lead, (torch.int32,), (ints, torch.int32))
+        act = self._stats_plane("actions", planes["actions"], lead, (torch.int32,))
+        nodes = self._stats_plane("nodes", planes["nodes"], lead, (torch.uint8,))
+        rew = self._stats_plane("rew", planes["rew"], lead, (torch.float32,))
+        term = self._stats_plane("term", planes["term"], lead, (torch.bool, torch.uint8))
+        trunc = self._stats_plane("trunc", planes["trunc"], lead, (torch.bool, torch.uint8))
+        o0 = self._stats_plane("obs0", obs0, (B,), (torch.int32,), (ints, torch.int32))
+        if next_nodes is None:
+            next_nodes = self.controller_nodes
+        nn = self._stats_plane("next_nodes", next_nodes, (B,), (torch.uint8,))
+        boot = None if bootstrap is None else self._stats_plane("bootstrap", bootstrap, (B,), (torch.float32,))
+        try:
+            P = self.query("controller_population")
+        except _lib.GymPoError:
+            P = 0  # a kind without populations
+        shape = ((P,) if P else ()) + (M, n_obs, A, M + 1)
+        if into is None:
+            into = {n: torch.zeros(shape, dtype=torch.int64, device=self.device) for n in ("counts", "ret_q")}
+        else:
+            if not isinstance(into, dict) or any(n not in into for n in ("counts", "ret_q")):
+                raise ValueError("controller_statistics: into must be a dict with 'counts' and 'ret_q'")
+            for n in ("counts", "ret_q"):
+                t = into[n]
+                if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.int64
+                        or t.device != self.device or not t.is_contiguous()):
+                    raise ValueError(f"controller_statistics: into[{n!r}] must be a contiguous int64 tensor of shape "
+                                     f"{shape} on {self.device}")
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        check(fn(self._handle, K, ptr(o0), ptr(obs), ptr(act), ptr(nodes), ptr(nn), ptr(rew), ptr(term), ptr(trunc),
+                 ptr(boot), float(gamma), ptr(into["counts"]), ptr(into["ret_q"]), self._stream()),
+              "gp_controller_stats")
+        return {"counts": into["counts"], "ret_q": into["ret_q"]}
+
     def autotune(self, K=20, reps=5):
         """Pick, on this device, the faster of the handle's interchangeable kernels for launches of K steps
         (numpy-mode FourRooms/ROOMS: the windowed and the fused kernel, bit-identical results) by timing `reps`

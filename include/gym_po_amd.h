@@ -397,6 +397,54 @@ int gp_set_controller_population(gp_env* env, int n_ctrl, int64_t group_envs, in
                                  const uint32_t* thr_host);
 int gp_controller_scores(gp_env* env, double* out, int cap_rows, int clear);
 
+/* ---- controller statistics: visit counts and return-to-go sums per table cell, exact integers ----
+ * The sufficient statistics of policy-gradient, Monte Carlo policy-iteration and EM steps over a controller's
+ * parameters, from K stored closed-loop steps, in one launch. Every kind with closed-loop rollouts (GRID, ROCKSAMPLE,
+ * ANTTAG, TAXI, HEAVENHELL, CROOMS); the others: GP_E_UNSUPPORTED. (No reference counterpart.)
+ *
+ * The call is a pure function of the planes it is given: it reads nothing of the env's state and needs no gp_reset.
+ * The handle supplies the shape: M = n_nodes and n_obs of the installed controller, A = the env's action count, and
+ * P, G of an installed population (P = 1 otherwise). GP_E_STATE without a controller or population. All pointers are
+ * device pointers on the handle's device; the call is asynchronous on `stream`.
+ *   obs0 int32 [B]: the obs before the first of the K steps; obs int32 [K,B]: the obs after each step (the scalar obs
+ *   plane of gp_rollout_controller); actions int32 [K,B]; nodes uint8 [K,B]: the node each action was chosen in;
+ *   next_nodes uint8 [B]: the nodes after the K-th step (gp_controller_nodes right after the rollout); rew float
+ *   [K,B]; term / trunc uint8 [K,B]; bootstrap float [B] or NULL (= 0): the value after the K-th step; gamma a
+ *   float32 in (0, 1] (else, NaN included, GP_E_INVALID).
+ *
+ * Tables. counts and ret_q are int64 [P][M][n_obs][A][M+1], 8-byte aligned (else GP_E_INVALID). The call ADDS to
+ * them; the caller zeroes them. Rows hold exactly A * (M + 1) entries, never the padded stride some kinds upload.
+ *
+ * Cell of a visit. Env e belongs to controller p = e / G. At step k: n = nodes[k][e]; o = k ? obs[k-1][e] : obs0[e],
+ * the obs the choice was conditioned on; a = actions[k][e]; ended = term[k][e] | trunc[k][e]; the last index is M if
+ * ended, else nodes[k+1][e] (next_nodes[e] for k = K - 1). Column M means "this choice ended the episode": the
+ * rollouts zero the node at episode end, so the planes do not hold the drawn next node there, and it has no effect on
+ * the return either; a gradient uses the action marginal for these visits.
+ *
+ * Return-to-go, float32. G_K = bootstrap ? bootstrap[e] : 0; for k = K-1 .. 0: G_k = ended ? rew[k][e]
+ * : fl32(rew[k][e] + fl32(gamma * G_{k+1})): two roundings, never contracted into an FMA. Truncation stops the return
+ * exactly as termination does (the discounted_return_sum convention of the population scores above).
+ *
+ * Accumulation. counts[cell] += 1; ret_q[cell] += rint(G_k * 2^20) as int64 (round to nearest even). The scaling by
+ * 2^20 is exact, so the only rounding is to units of 2^-20: at most 2^-21 per visit. Integer sums do not depend on the
+ * order of the adds: the tables are bit-reproducible and independent of the launch geometry (no float atomics).
+ * Overflow: an entry of ret_q overflows once the sum of |G| over its visits reaches 2^43 (2^63 / 2^20); the caller
+ * reads and clears the tables before that.
+ *
+ * Bad visits. A visit whose node is >= M, whose obs is outside [0, n_obs), whose action is outside [0, A), whose
+ * non-ended next node is >= M, or with !(|G_k| < 2^31) (NaN and infinity included) is skipped, never clamped into
+ * another cell, and flags the handle: gp_check then returns GP_E_DEVICE until the next seed. The G chain goes on
+ * through the visit.
+ *
+ * Paths. When one controller's tables fit an LDS budget (12 B per cell; default 40 KiB, the knob "stats_lds_max"
+ * below) each block keeps a private histogram in LDS and adds its non-zero cells to the tables at its end; otherwise
+ * (and for K >= 2^22) every visit is a 64-bit integer atomic on the tables. The results are identical bit for bit.
+ * gp_query "stats_lds": which one the handle's last call took (1 LDS, 0 global, -1 none yet). K = 0 is a no-op. */
+int gp_controller_stats(gp_env* env, int K, const int32_t* obs0, const int32_t* obs, const int32_t* actions,
+                        const uint8_t* nodes, const uint8_t* next_nodes, const float* rew, const uint8_t* term,
+                        const uint8_t* trunc, const float* bootstrap, float gamma, int64_t* counts, int64_t* ret_q,
+                        void* stream);
+
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
@@ -431,7 +479,7 @@ int gp_metrics(gp_env* env, double out[4]);
  * device (numpy-mode GRID: a persistent kernel's cross-block wait timed out; any kind: an action outside
  * [-n, n) was given, where the reference raises IndexError at msrooms.py:400 / rooms.py:208 /
  * extended_taxi.py:248 — the device clamps it and flags the handle; closed-loop rollouts: an obs or node outside the
- * controller table, clamped and flagged likewise), else GP_OK. The
+ * controller table, clamped and flagged likewise; gp_controller_stats: a visit it had to skip), else GP_OK. The
  * asynchronous step/rollout calls cannot report such failures themselves; gp_metrics and
  * gp_get_rng_state run the same check. (No reference counterpart: numpy steps are synchronous.) */
 int gp_check(gp_env* env);
@@ -451,7 +499,10 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * ANTTAG, TAXI, HEAVENHELL and CROOMS answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
  * rollout, 0 = no controller). GRID also: "controller_population" (P of the installed population, 0 = none),
  * "controller_group_envs" (its G), "controller_group_multiple" (1024: what G must be a multiple of); with a population
- * "controller_nodes" and "controller_lds" answer for one controller's table. Unknown keys return
+ * "controller_nodes" and "controller_lds" answer for one controller's table. Every kind with closed-loop rollouts
+ * also: "controller_n_obs" and "controller_actions" (n_obs of the installed table and the env's A: the shape
+ * gp_controller_stats uses; GP_E_STATE without a controller), "stats_lds" (the path of the handle's last
+ * gp_controller_stats launch: 1 LDS histogram, 0 global atomics, -1 none yet). Unknown keys return
  * GP_E_INVALID. */
 int gp_query(const gp_env* env, const char* key, int64_t* value);
 /* ---- the normal sampler of rng_mode=philox (C-ROOMS noise), diagnostics ----
@@ -505,7 +556,10 @@ int gp_profile_read_resolver(gp_env* env, double* total_ms, int64_t* n_launches)
  *   gp_set_controller instead: the controller table is staged in LDS when the env's tables plus the table take at
  *   most this many bytes of LDS per block, at most 60 KB; 0 = always read from global memory, -1 = the default,
  *   32 KB), "persist_bpc" (TAXI / CROOMS / ANTTAG / ROCKSAMPLE / HEAVENHELL persistent rollouts: blocks per CU, 0 = every
- *   resident block; TAXI keeps the value it was created with for its closed-loop grid too).
+ *   resident block; TAXI keeps the value it was created with for its closed-loop grid too), "stats_lds_max"
+ *   (gp_controller_stats, read at every call instead: one controller's tables are accumulated in a block-private LDS
+ *   histogram when they take at most this many bytes, 12 per cell, at most 60 KB; 0 = always global atomics, -1 = the
+ *   default, 40 KiB).
  *   gp_debug_reset restores the defaults. Unknown key: GP_E_INVALID. */
 int gp_debug_set(const char* key, int64_t value);
 void gp_debug_reset(void);
