@@ -37,11 +37,6 @@ constexpr int MAX_SIZE = 16;  // cells fit 8 bits of the packed state
 constexpr int NACT = 5;
 constexpr uint32_t TAG = 0x616e7431u;  // 'ant1'
 
-struct alignas(32) AtSlot {
-  double return_sum;
-  unsigned long long episodes, length_sum, env_steps;
-};
-
 struct AtDev {
   int32_t B, ntiles, N, ncells;
   uint32_t divm;           // ceil(2^16 / N): cell / N == (cell * divm) >> 16 for cells < 256
@@ -51,7 +46,7 @@ struct AtDev {
   const uint8_t* tabs;     // [ncells] valid-target counts (u8, 16-B padded) | [ncells][ncells] target lists
   int32_t off_cnt, off_list, tab_bytes;
   uint32_t* st;            // [B] ant | target << 8 | elapsed << 16
-  AtSlot* mslot;
+  MetricSlot* mslot;
   uint32_t* derr;            // device error word (GP_DERR_*)
   const int32_t* rp_choose;  // replay: target move choice [B]
   const int32_t* rp_ant;     // replay: reset ant cell index [B]
@@ -88,6 +83,8 @@ __device__ __forceinline__ uint32_t draw_reset(const AtDev& p, const uint8_t* ld
   return ant | (tgt << 8);
 }
 
+// (this file's own copy of gp_common.h's StepOut, inside the unnamed namespace: the symbol names of at_env_step's
+// constant tables DY / DX spell out its return type)
 struct StepOut {
   float rew;
   uint8_t term, trunc;
@@ -149,35 +146,6 @@ __device__ __forceinline__ int4 at_obs(const AtDev& p, uint32_t u) {
   const int dy = ay - ty, dx = ax - tx;
   const bool vis = dy * dy + dx * dx < p.vis_r2;
   return make_int4(ay, ax, vis ? ty : -1, vis ? tx : -1);
-}
-
-__device__ void at_metrics(const AtDev& p, float rsum, uint32_t eps, uint32_t lens, uint32_t nst) {
-  __shared__ float s_r[WAVES];
-  __shared__ uint32_t s_e[WAVES], s_l[WAVES], s_n[WAVES];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float r = 0.f;
-    unsigned long long e = 0, l = 0, n = 0;
-    for (int w = 0; w < WAVES; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
-    AtSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
-    m.episodes += e;
-    m.length_sum += l;
-    m.env_steps += n;
-  }
-}
-
-__device__ __forceinline__ bool quad_ok(const void* base, int env0, int B, int esz) {
-  return env0 + 3 < B && ((((uintptr_t)base) + (size_t)env0 * esz) & (size_t)(4 * esz - 1)) == 0;
 }
 
 template <bool REPLAY>
@@ -267,7 +235,7 @@ __global__ __launch_bounds__(TPB, GP_AT_WAVES) void anttag_rollout(AtDev p, int 
         if (env0 + i < p.B) p.st[env0 + i] = u[i];
     }
   }
-  at_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 template <bool REPLAY>
@@ -289,46 +257,6 @@ __device__ __forceinline__ int32_t at_obs_idx(const AtDev& p, uint32_t u) {
   const int ay = cdiv(p, ant), ax = ant - ay * N, ty = cdiv(p, tgt), tx = tgt - ty * N;
   const int dy = ay - ty, dx = ax - tx;
   return ant * (p.ncells + 1) + (dy * dy + dx * dx < p.vis_r2 ? tgt : p.ncells);
-}
-
-// A thread's 4 consecutive envs as one access (16 B of 4-byte elements, 4 B of flags) when quad_ok, else element by
-// element (the ragged tail, caller buffers off their boundary): chosen per buffer and per step, as in rocksample.hip.
-template <class T>
-__device__ __forceinline__ void load4(const T* b, int env0, int B, T (&v)[EPT]) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
-  if (quad_ok(b, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      const uint4 q = *reinterpret_cast<const uint4*>(b + env0);
-      const uint32_t w[EPT] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = __builtin_bit_cast(T, w[i]);
-    } else {
-      const uint32_t q = *reinterpret_cast<const uint32_t*>(b + env0);
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = (T)((q >> (8 * i)) & 0xFFu);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) v[i] = env0 + i < B ? b[env0 + i] : T(0);
-  }
-}
-template <class T>
-__device__ __forceinline__ void store4(T* b, int env0, int B, const T (&v)[EPT]) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
-  if (quad_ok(b, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<uint4*>(b + env0) =
-          make_uint4(__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
-                     __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3]));
-    } else {
-      *reinterpret_cast<uint32_t*>(b + env0) =
-          (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i)
-      if (env0 + i < B) b[env0 + i] = v[i];
-  }
 }
 
 // K steps of every env with the index obs: the geometry of anttag_rollout (persistent grid-stride loop over 1,024-env
@@ -359,10 +287,7 @@ __global__ __launch_bounds__(TPB) void anttag_rollout_idx(AtDev p, CtrlDev c, in
       load4<uint8_t>(c.node, env0, p.B, nd);
 #pragma unroll
       for (int i = 0; i < EPT; ++i)
-        if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
-          if (env0 + i < p.B) atomicOr(p.derr, GP_DERR_CTRL);
-          nd[i] = (uint8_t)(c.M - 1);
-        }
+        ctrl_clamp_node(nd[i], c.M, env0 + i < p.B, p.derr);
     } else {
       if (K > 0) load4<int32_t>(act, env0, p.B, a_nxt);
     }
@@ -380,14 +305,8 @@ __global__ __launch_bounds__(TPB) void anttag_rollout_idx(AtDev p, CtrlDev c, in
           const uint32_t y = env < p.B ? philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG,
                                                        p.key0, p.key1).x[0] >> 1
                                        : 0u;
-          uint32_t o = (uint32_t)at_obs_idx(p, u[i]);
-          if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
-            if (env < p.B) atomicOr(p.derr, GP_DERR_CTRL);
-            o = (uint32_t)c.n_obs - 1u;
-          }
-          const uint32_t* row = c.thr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
-          jj[i] = min(ctrl_search(row, c.L, y), lreal - 1u);
-          a[i] = (int32_t)((jj[i] * c.inv_m) >> 16);  // j / M
+          jj[i] = ctrl_pick(c.thr, nd[i], c.n_obs, c.L, lreal, (uint32_t)at_obs_idx(p, u[i]), y, env < p.B, p.derr);
+          a[i] = (int32_t)ctrl_action(jj[i], c.inv_m);
           n4[i] = nd[i];
         }
       } else {
@@ -407,8 +326,8 @@ __global__ __launch_bounds__(TPB) void anttag_rollout_idx(AtDev p, CtrlDev c, in
         tr[i] = o.trunc;
         ob[i] = at_obs_idx(p, u[i]);
         nst += live ? 1u : 0u;
-        if constexpr (CTRL)  // j % M; episode end: node 0
-          nd[i] = (o.term | o.trunc) ? (uint8_t)0 : (uint8_t)(jj[i] - (uint32_t)a[i] * (uint32_t)c.M);
+        if constexpr (CTRL)  // episode end: node 0
+          nd[i] = (o.term | o.trunc) ? (uint8_t)0 : (uint8_t)ctrl_node(jj[i], (uint32_t)a[i], c.M);
       }
       if constexpr (CTRL) {
         if (aout) store4<int32_t>(aout + off, env0, p.B, a);
@@ -422,7 +341,7 @@ __global__ __launch_bounds__(TPB) void anttag_rollout_idx(AtDev p, CtrlDev c, in
     store4<uint32_t>(p.st, env0, p.B, u);
     if constexpr (CTRL) store4<uint8_t>(c.node, env0, p.B, nd);
   }
-  at_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 template <bool REPLAY>
@@ -458,13 +377,13 @@ __global__ void anttag_set_state(AtDev p, const int32_t* ant, const int32_t* tgt
 // ------------------------------------------------------------------ host backend ----
 struct AntTagBackend : EnvBackend {
   AtDev d{};
-  CtrlDev ctrl{};          // M == 0: no controller installed
+  CtrlHost ctrl;
   bool obs_index = false;  // the scalar index obs (anttag_rollout_idx / anttag_reset_idx) instead of the vector
   int grid = 1;            // blocks of the handle's open-loop rollout (and reset) kernel
   int grid_ctrl = 1;       // blocks of the closed-loop rollout (index obs, philox)
   int nslot = 1;           // metric slots: the larger of the two grids
   uint64_t philox_step = 0;
-  DevBuf b_tabs, b_st, b_slot, b_cthr, b_cnode;
+  DevBuf b_tabs, b_st, b_slot;
   DevErr derr;
   const int32_t* rp_choose = nullptr;
   const int32_t* rp_ant = nullptr;
@@ -496,14 +415,14 @@ struct AntTagBackend : EnvBackend {
   }
   int query(const char* key, int64_t* v) const override {
     if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
-    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.dev.M;  // node count of the installed controller (0 = none)
     else if (!strcmp(key, "controller_lds")) *v = 0;         // the table is read from global memory
     else return EnvBackend::query(key, v);
     return GP_OK;
   }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(AtSlot) * nslot, s));
-    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * nslot, s));
+    if (int e = ctrl.reset_nodes(B, s)) return e;
     const AtDev dd = dev_for_launch();
     if (rng_mode == GP_RNG_REPLAY) {
       if (!rp_ant || !rp_tgt) {
@@ -574,18 +493,14 @@ struct AntTagBackend : EnvBackend {
     gp_set_error("%s: anttag runs controllers on the index obs (obs_index = 1) in GP_RNG_PHILOX only", what);
     return GP_E_UNSUPPORTED;
   }
-  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, NACT, 0, 0, derr.ptr(), out); }
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.dev.M, ctrl.dev.n_obs, NACT, 0, 0, derr.ptr(), out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override {
     if (int e = ctrl_supported("gp_rollout_controller")) return e;
-    if (!has_reset || !ctrl.M) {
-      gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
-                                                                        "(gp_set_controller)");
-      return GP_E_STATE;
-    }
+    if (int e = ctrl.ready(has_reset)) return e;
     timer.begin(s);
-    hipLaunchKernelGGL((anttag_rollout_idx<false, true>), dim3(grid_ctrl), dim3(TPB), d.tab_bytes, s, d, ctrl, K,
+    hipLaunchKernelGGL((anttag_rollout_idx<false, true>), dim3(grid_ctrl), dim3(TPB), d.tab_bytes, s, d, ctrl.dev, K,
                        philox_step, (const int32_t*)nullptr, (int32_t*)obs, act, nodes, rew, term, trunc);
     timer.end(s);
     philox_step += (uint64_t)K;
@@ -594,13 +509,7 @@ struct AntTagBackend : EnvBackend {
   }
   int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
     if (int e = ctrl_supported("gp_controller_nodes")) return e;
-    if (!ctrl.M) {
-      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
-      return GP_E_STATE;
-    }
-    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
-    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
-    return GP_OK;
+    return ctrl.nodes(get, set, B, s);
   }
   int step(const void* act, void* obs, float* rew, uint8_t* term, uint8_t* trunc, hipStream_t s) override {
     return rollout(1, act, obs, rew, term, trunc, s);
@@ -631,55 +540,18 @@ struct AntTagBackend : EnvBackend {
   }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<AtSlot> m(nslot);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(AtSlot) * nslot, hipMemcpyDeviceToHost));
-    out[0] = out[1] = out[2] = out[3] = 0;
-    for (const AtSlot& x : m) {
-      out[0] += (double)x.episodes;
-      out[1] += x.return_sum;
-      out[2] += (double)x.length_sum;
-      out[3] += (double)x.env_steps;
-    }
+    std::vector<MetricSlot> m(nslot);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(MetricSlot) * nslot, hipMemcpyDeviceToHost));
+    sum_metric_slots(m.data(), m.size(), out);
     return check();
   }
 };
 
-// thr_host rows hold L = 5 M entries (M <= 8: L <= 40, below the 64 up to which j / M by inv_m is exact); L is no
-// multiple of 4 in general, so each uploaded row is padded to a multiple of 4 entries with 2^31 (never counted:
-// y < 2^31) and ctrl_search keeps its 16-B quads.
+// L = 5 M is no multiple of 4 in general: CtrlHost::install pads the rows. The table is read from global memory.
 int AntTagBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
   if (int e = ctrl_supported("gp_set_controller")) return e;
-  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
-  if (!thr_host) {
-    ctrl = CtrlDev{};
-    int e;
-    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
-    return GP_OK;
-  }
-  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
-    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
-    return GP_E_INVALID;
-  }
-  const int L = NACT * n_nodes, Lp = (L + 3) & ~3;
-  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)Lp;
-  if (n > ((size_t)1 << 28)) {
-    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
-    return GP_E_INVALID;
-  }
-  std::vector<uint32_t> padded(n);
-  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L, Lp, padded.data())) return e;
-  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
-  int e;
-  if ((e = b_cthr.upload(padded)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
-  ctrl.thr = b_cthr.as<uint32_t>();
-  ctrl.node = b_cnode.as<uint8_t>();
-  ctrl.M = n_nodes;
-  ctrl.n_obs = n_obs;
-  ctrl.L = Lp;
-  ctrl.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
-  ctrl.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
-  ctrl.lds_off = -1;
-  return GP_OK;
+  if (!thr_host) return ctrl.clear();
+  return ctrl.install("gp_set_controller", NACT, n_nodes, n_obs, thr_host, B);
 }
 
 int AntTagBackend::build(const gp_anttag_config* cfg) {
@@ -765,8 +637,8 @@ int AntTagBackend::build(const gp_anttag_config* cfg) {
     grid_ctrl = persistent_grid(d.ntiles, prop.multiProcessorCount, occ_c);
     nslot = std::max(grid, grid_ctrl);
   }
-  if ((e = b_slot.alloc(sizeof(AtSlot) * nslot))) return e;
-  d.mslot = b_slot.as<AtSlot>();
+  if ((e = b_slot.alloc(sizeof(MetricSlot) * nslot))) return e;
+  d.mslot = b_slot.as<MetricSlot>();
   if ((e = derr.alloc())) return e;
   d.derr = derr.ptr();
   return GP_OK;

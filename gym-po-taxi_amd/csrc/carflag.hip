@@ -42,11 +42,6 @@ constexpr int MAX_TIME_LIMIT = 1 << 29;
 enum { ACT_F32 = 0, ACT_F64 = 1, ACT_DISC = 2 };
 enum { M_PHILOX = 0, M_REPLAY = 1, M_NUMPY = 2 };
 
-struct alignas(32) CfSlot {
-  double return_sum;
-  unsigned long long episodes, length_sum, env_steps;
-};
-
 // numpy's PCG64 position on the device (the increment stays on the host: the jump tables carry it)
 struct alignas(32) CfRng {
   uint64_t s_hi, s_lo;
@@ -59,7 +54,7 @@ struct CfDev {
   uint32_t key0, key1;
   float4* st;               // [B] x, v, direction, bits(heaven | priest << 1 | elapsed << 2)
   const double* table;      // [nact] discrete action table (np.linspace(-1, 1, n))
-  CfSlot* mslot;
+  MetricSlot* mslot;
   uint32_t* derr;
   uint32_t* tile_cnt;       // numpy mode: pending resets per tile of the current step
   const PcgJump* jt;        // numpy mode: radix-64 jump tables of the stream's increment
@@ -92,11 +87,6 @@ __device__ __forceinline__ void set_reset(CfEnv& e, uint64_t k53, uint32_t hbit,
   e.dir = 0.f;
   e.w = (hbit & 1u) | ((pbit & 1u) << 1);
 }
-
-struct StepOut {
-  float rew;
-  uint8_t term, trunc;
-};
 
 // One env, one step (reset excluded). F64: the float64-action arithmetic.
 template <bool F64>
@@ -139,34 +129,6 @@ __device__ __forceinline__ StepOut cf_dyn(const CfDev& p, CfEnv& e, double a64, 
   return o;
 }
 
-// lens is 64-bit from the thread on: one episode can be 2^29 steps long (MAX_TIME_LIMIT), so four envs of a thread
-// that end together already sum to 2^31 and two such threads wrapped a 32-bit wave sum to 0.
-__device__ void cf_metrics(const CfDev& p, float rsum, uint32_t eps, unsigned long long lens, uint32_t nst) {
-  __shared__ float s_r[WAVES];
-  __shared__ uint32_t s_e[WAVES], s_n[WAVES];
-  __shared__ unsigned long long s_l[WAVES];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float r = 0.f;
-    unsigned long long e = 0, l = 0, n = 0;
-    for (int w = 0; w < WAVES; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
-    CfSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
-    m.episodes += e;
-    m.length_sum += l;
-    m.env_steps += n;
-  }
-}
-
 __device__ __forceinline__ bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
 // Four actions of one thread: 16-B loads where the address allows, scalars at the ragged end.
@@ -206,6 +168,8 @@ __global__ __launch_bounds__(TPB) void cf_rollout(CfDev p, int K, uint64_t step0
   float4* wv = s_obs + wid * 64 * 3;
   float rsum = 0.f;
   uint32_t eps = 0, nst = 0;
+  // lens is 64-bit from the thread on: one episode can be 2^29 steps long (MAX_TIME_LIMIT), so four envs of a thread
+  // that end together already sum to 2^31 and two such threads wrapped a 32-bit wave sum to 0 (block_metrics' LT)
   unsigned long long lens = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;
@@ -322,7 +286,7 @@ __global__ __launch_bounds__(TPB) void cf_rollout(CfDev p, int K, uint64_t step0
       __syncthreads();
     }
   }
-  cf_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 // Numpy-mode resets of one step (ALL: of reset(), every env). One block per tile. With b the number of
@@ -512,7 +476,7 @@ struct CarFlagBackend : EnvBackend {
   }
   bool replay_ready() const { return d.rp_u && d.rp_h && d.rp_p; }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(CfSlot) * grid, s));
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * grid, s));
     const unsigned nb = (unsigned)((B + TPB - 1) / TPB);
     if (rng_mode == GP_RNG_NUMPY) {
       hipLaunchKernelGGL(cf_resolve<true>, dim3(d.ntiles), dim3(TPB), 0, s, d, par, (float*)obs);
@@ -607,15 +571,9 @@ struct CarFlagBackend : EnvBackend {
   }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<CfSlot> m(grid);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(CfSlot) * grid, hipMemcpyDeviceToHost));
-    out[0] = out[1] = out[2] = out[3] = 0;
-    for (const CfSlot& x : m) {
-      out[0] += (double)x.episodes;
-      out[1] += x.return_sum;
-      out[2] += (double)x.length_sum;
-      out[3] += (double)x.env_steps;
-    }
+    std::vector<MetricSlot> m(grid);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(MetricSlot) * grid, hipMemcpyDeviceToHost));
+    sum_metric_slots(m.data(), m.size(), out);
     return check();
   }
 };
@@ -653,8 +611,8 @@ int CarFlagBackend::build(const gp_carflag_config* cfg) {
   grid = persistent_grid(d.ntiles, prop.multiProcessorCount, occ);
   persist_grid = grid;
   persist_occ = occ;
-  if ((e = b_slot.alloc(sizeof(CfSlot) * grid))) return e;
-  d.mslot = b_slot.as<CfSlot>();
+  if ((e = b_slot.alloc(sizeof(MetricSlot) * grid))) return e;
+  d.mslot = b_slot.as<MetricSlot>();
   if ((e = derr.alloc())) return e;
   d.derr = derr.ptr();
   if (rng_mode == GP_RNG_NUMPY) {

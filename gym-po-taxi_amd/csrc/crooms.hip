@@ -62,10 +62,6 @@ constexpr uint32_t TAG_DRAW = 0x6d733121u;
 constexpr double MAX_VELOCITY = 5.0;
 // Largest batch of the exact (numpy-stream) mode, which runs in one workgroup.
 
-struct alignas(32) CrSlot {
-  double return_sum;
-  unsigned long long episodes, length_sum, env_steps;
-};
 
 // observation kinds handled here (GP_OBS_F32 = continuous coordinates)
 struct CrDev {
@@ -88,7 +84,7 @@ struct CrDev {
   double* vx;
   uint32_t* goal;        // gy | gx << 16 (int16 each; a fixed goal may lie off the grid)
   int32_t* el;
-  CrSlot* mslot;
+  MetricSlot* mslot;
   int32_t nslot;         // metric slots (the exact-mode step kernel spreads its blocks' atomics over them)
   uint32_t* derr;        // device error word (GP_DERR_*)
   // replay
@@ -538,32 +534,6 @@ __device__ __forceinline__ StepOut crooms_env_step(const CrDev& p, const uint8_t
   return o;
 }
 
-// Per-block metrics into the block's own slot.
-__device__ void cr_metrics(const CrDev& p, float rsum, uint32_t eps, uint32_t lens, uint32_t nst) {
-  __shared__ float s_r[WAVES];
-  __shared__ uint32_t s_e[WAVES], s_l[WAVES], s_n[WAVES];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float r = 0.f;
-    unsigned long long e = 0, l = 0, n = 0;
-    for (int w = 0; w < WAVES; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
-    CrSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
-    m.episodes += e;
-    m.length_sum += l;
-    m.env_steps += n;
-  }
-}
-
 // ---- the rollout kernel: K steps for every env; 2 consecutive envs per thread ----
 template <int OK, bool REPLAY, int SPEC = 0>
 __global__ __launch_bounds__(TPB, GP_CR_WAVES) void crooms_rollout(CrDev p, int K, uint64_t step0, const void* __restrict__ act,
@@ -679,7 +649,7 @@ __global__ __launch_bounds__(TPB, GP_CR_WAVES) void crooms_rollout(CrDev p, int 
       p.el[env] = el[i];
     }
   }
-  cr_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 // ---- the closed-loop rollout kernel (gp_rollout_controller; semantics in include/gym_po_amd.h) ----
@@ -758,10 +728,7 @@ __global__ __launch_bounds__(TPB, GP_CR_CTRL_WAVES) void crooms_rollout_ctrl(
                   : 0u;
       el[i] = live ? p.el[env] : 0;
       nd[i] = live ? (uint32_t)cnode[env] : 0u;
-      if (nd[i] >= (uint32_t)cM) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
-        if (live) atomicOr(p.derr, GP_DERR_CTRL);
-        nd[i] = (uint32_t)cM - 1u;
-      }
+      ctrl_clamp_node(nd[i], cM, live, p.derr);
       ob[i] = cr_scalar_obs<OK>(p, lds, ay[i], ax[i], g[i]);
     }
     for (int k = 0; k < K; ++k) {
@@ -778,14 +745,8 @@ __global__ __launch_bounds__(TPB, GP_CR_CTRL_WAVES) void crooms_rollout_ctrl(
         const uint32_t y =
             live ? philox4x32_10((uint32_t)env, (uint32_t)stp, (uint32_t)(stp >> 32), CTRL_TAG, p.key0, p.key1).x[0] >> 1
                  : 0u;
-        uint32_t o = (uint32_t)ob[i];
-        if (o >= cNobs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
-          if (live) atomicOr(p.derr, GP_DERR_CTRL);
-          o = cNobs - 1u;
-        }
-        const uint32_t* row = cthr + ((size_t)nd[i] * (size_t)cNobs + o) * (size_t)cL;
-        jj[i] = min(ctrl_search(row, cL, y), (uint32_t)cL - 1u);  // (< L by the row's last entry, 2^31 > y)
-        a[i] = (int32_t)((jj[i] * cInv) >> 16);                   // j / M
+        jj[i] = ctrl_pick(cthr, nd[i], cNobs, cL, (uint32_t)cL, (uint32_t)ob[i], y, live, p.derr);
+        a[i] = (int32_t)ctrl_action(jj[i], cInv);
         n2[i] = (uint8_t)nd[i];
       }
       float r[EPT];
@@ -801,7 +762,7 @@ __global__ __launch_bounds__(TPB, GP_CR_CTRL_WAVES) void crooms_rollout_ctrl(
         tr[i] = o.trunc;
         nst += live ? 1u : 0u;
         ob[i] = cr_scalar_obs<OK>(p, lds, ay[i], ax[i], g[i]);
-        nd[i] = (o.term | o.trunc) ? 0u : jj[i] - (uint32_t)a[i] * (uint32_t)cM;  // j % M; episode end: node 0
+        nd[i] = (o.term | o.trunc) ? 0u : ctrl_node(jj[i], (uint32_t)a[i], cM);  // episode end: node 0
       }
       if (full) {
         if (aout) *reinterpret_cast<int2*>(aout + off + env0) = make_int2(a[0], a[1]);
@@ -834,7 +795,7 @@ __global__ __launch_bounds__(TPB, GP_CR_CTRL_WAVES) void crooms_rollout_ctrl(
       cnode[env] = (uint8_t)nd[i];
     }
   }
-  cr_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 // reset(): goal then agent for every env (crooms.py:251-266).
@@ -1317,7 +1278,7 @@ __global__ __launch_bounds__(XT) void crooms_numpy_rollout(CrDev p, CrExact x, i
   }
   __syncthreads();
   if (t == 0) {
-    CrSlot& m = p.mslot[0];
+    MetricSlot& m = p.mslot[0];
     m.return_sum += (double)m_r;
     m.episodes += m_e;
     m.length_sum += m_l;
@@ -2426,7 +2387,7 @@ __global__ __launch_bounds__(XGT) void xg_step(CrDev p, XgFlags fd, XgFlags fs, 
     float r = 0.f;
     uint32_t ee = 0, l = 0, nn = 0;
     for (int i = 0; i < XGW; ++i) { r += m_r[i]; ee += m_e[i]; l += m_l[i]; nn += m_n[i]; }
-    CrSlot& m = p.mslot[blockIdx.x % p.nslot];  // (one slot for every block serialised up to 6 us of atomics)
+    MetricSlot& m = p.mslot[blockIdx.x % p.nslot];  // (one slot for every block serialised up to 6 us of atomics)
     atomicAdd(&m.return_sum, (double)r);
     atomicAdd(&m.episodes, (unsigned long long)ee);
     atomicAdd(&m.length_sum, (unsigned long long)l);
@@ -2501,27 +2462,18 @@ struct CRoomsBackend : EnvBackend {
   DevBuf b_tabs, b_ay, b_ax, b_vy, b_vx, b_goal, b_el, b_slot;
   DevErr derr;
   // closed-loop rollouts (gp_set_controller; philox mode, a scalar obs, discrete actions)
-  CtrlDev ctrl{};  // M == 0: no controller installed
+  CtrlHost ctrl;
   int grid_ctrl = 1, cus = 1;
   size_t lds_ctrl = 0;  // dynamic LDS of the closed-loop launches
-  DevBuf b_cthr, b_cnode;
-  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, d.nact, 0, 0, derr.ptr(), out); }
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.dev.M, ctrl.dev.n_obs, d.nact, 0, 0, derr.ptr(), out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override;
-  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
-    if (!ctrl.M) {
-      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
-      return GP_E_STATE;
-    }
-    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
-    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
-    return GP_OK;
-  }
+  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override { return ctrl.nodes(get, set, B, s); }
   int query(const char* key, int64_t* v) const override {
     if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
-    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
-    else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.dev.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = ctrl.dev.M && ctrl.dev.lds_off >= 0;  // its table is staged in LDS
     else return EnvBackend::query(key, v);
     return GP_OK;
   }
@@ -2805,8 +2757,8 @@ struct CRoomsBackend : EnvBackend {
     return dd;
   }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(CrSlot) * grid, s));
-    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * grid, s));
+    if (int e = ctrl.reset_nodes(B, s)) return e;
     if (rng_mode == GP_RNG_REPLAY && ((!d.goal_fixed && !rp_goal) || (!d.agent_fixed && !rp_agent))) {
       gp_set_error("crooms replay reset needs goal/agent index draws (gp_set_replay i0/i1)");
       return GP_E_STATE;
@@ -2920,15 +2872,9 @@ struct CRoomsBackend : EnvBackend {
   }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<CrSlot> m(grid);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(CrSlot) * grid, hipMemcpyDeviceToHost));
-    out[0] = out[1] = out[2] = out[3] = 0;
-    for (const CrSlot& x : m) {
-      out[0] += (double)x.episodes;
-      out[1] += x.return_sum;
-      out[2] += (double)x.length_sum;
-      out[3] += (double)x.env_steps;
-    }
+    std::vector<MetricSlot> m(grid);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(MetricSlot) * grid, hipMemcpyDeviceToHost));
+    sum_metric_slots(m.data(), m.size(), out);
     return check();  // device errors (invalid actions; numpy mode: an invalid stream) invalidate the run
   }
 };
@@ -3176,8 +3122,8 @@ int CRoomsBackend::build(const gp_crooms_config* cfg) {
   grid_ctrl = grid;
   persist_grid = grid;
   persist_occ = occ;
-  if ((e = b_slot.alloc(sizeof(CrSlot) * grid))) return e;
-  d.mslot = b_slot.as<CrSlot>();
+  if ((e = b_slot.alloc(sizeof(MetricSlot) * grid))) return e;
+  d.mslot = b_slot.as<MetricSlot>();
   d.nslot = grid;
   if ((e = derr.alloc())) return e;
   d.derr = derr.ptr();
@@ -3188,10 +3134,8 @@ int CRoomsBackend::build(const gp_crooms_config* cfg) {
 }
 
 // Closed-loop rollouts need the philox draws, a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE) and discrete actions.
-// thr_host rows hold L = A M entries (A = 4 or 8, M <= 8: L <= 64, up to which j / M by inv_m is exact): whole 16-B
-// quads, uploaded as they are. The table is staged in LDS behind the env's tables when both fit CTRL_LDS_BUDGET (knob
-// ctrl_lds_max, at most 60 KB: with the 64 B of static LDS a launch stays below 64 KB); the closed-loop grid is sized
-// from the kernel's occupancy at that dynamic-LDS size and never exceeds the open loop's (one set of metric slots).
+// A = 4 or 8: rows of whole 16-B quads. The closed-loop grid is sized from the kernel's occupancy at the launch's
+// dynamic-LDS size (CtrlHost::stage) and never exceeds the open loop's (one set of metric slots).
 int CRoomsBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
   if (rng_mode != GP_RNG_PHILOX) {
     gp_set_error("crooms: controllers need rng_mode philox (%s mode has no counter-based draw for the controller)",
@@ -3207,64 +3151,24 @@ int CRoomsBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_ho
                  "vector, window or continuous obs kind %d", d.obs_kind);
     return GP_E_UNSUPPORTED;
   }
-  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
-  if (!thr_host) {
-    ctrl = CtrlDev{};
-    int e;
-    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
-    return GP_OK;
-  }
-  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
-    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
-    return GP_E_INVALID;
-  }
-  const int L = d.nact * n_nodes;
-  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)L;
-  if (n > ((size_t)1 << 28)) {
-    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
-    return GP_E_INVALID;
-  }
-  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L)) return e;
-  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
-  std::vector<uint32_t> host(thr_host, thr_host + n);
-  int e;
-  if ((e = b_cthr.upload(host)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
-  CtrlDev c{};
-  c.thr = b_cthr.as<uint32_t>();
-  c.node = b_cnode.as<uint8_t>();
-  c.M = n_nodes;
-  c.n_obs = n_obs;
-  c.L = L;
-  c.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
-  c.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
-  const int knob = gp_debug_knobs().ctrl_lds_max;
-  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
-  const bool staged = (size_t)d.tab_bytes + n * sizeof(uint32_t) <= budget;
-  c.lds_off = staged ? d.tab_bytes : -1;
-  lds_ctrl = (size_t)d.tab_bytes + (staged ? n * sizeof(uint32_t) : 0);
+  if (!thr_host) return ctrl.clear();
+  if (int e = ctrl.install("gp_set_controller", d.nact, n_nodes, n_obs, thr_host, B)) return e;
+  lds_ctrl = ctrl.stage((size_t)d.tab_bytes, true);
+  const bool hansen = d.obs_kind == GP_OBS_HANSEN, staged = ctrl.dev.lds_off >= 0;
+  using Kern = void (*)(CrDev, CtrlDev, int, uint64_t, int32_t*, int32_t*, uint8_t*, float*, uint8_t*, uint8_t*);
+  const Kern kern = hansen ? (staged ? crooms_rollout_ctrl<GP_OBS_HANSEN, true> : crooms_rollout_ctrl<GP_OBS_HANSEN, false>)
+                           : (staged ? crooms_rollout_ctrl<GP_OBS_TABLE, true> : crooms_rollout_ctrl<GP_OBS_TABLE, false>);
   int occ = 0;
-  const bool hansen = d.obs_kind == GP_OBS_HANSEN;
-  if (hansen && staged) {
-    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_HANSEN, true>, TPB, lds_ctrl));
-  } else if (hansen) {
-    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_HANSEN, false>, TPB, lds_ctrl));
-  } else if (staged) {
-    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_TABLE, true>, TPB, lds_ctrl));
-  } else {
-    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, crooms_rollout_ctrl<GP_OBS_TABLE, false>, TPB, lds_ctrl));
-  }
+  const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, TPB, lds_ctrl);
+  if (he != hipSuccess) ctrl.dev = CtrlDev{};  // (no controller, as after a failed allocation)
+  GP_HIP_CHECK(he);
   grid_ctrl = std::min(persistent_grid(d.ntiles, cus, occ), grid);
-  ctrl = c;
   return GP_OK;
 }
 
 int CRoomsBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term,
                                       uint8_t* trunc, hipStream_t s) {
-  if (!has_reset || !ctrl.M) {
-    gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
-                                                                      "(gp_set_controller)");
-    return GP_E_STATE;
-  }
+  if (int e = ctrl.ready(has_reset)) return e;
   // the kernel's pair stores: 8 B of 4-byte elements, 2 B of flags (null: not stored)
   auto al = [](const void* x, uintptr_t m) { return ((uintptr_t)x & (m - 1)) == 0; };
   if (!al(act, 8) || !al(obs, 8) || !al(rew, 8) || !al(nodes, 2) || !al(term, 2) || !al(trunc, 2)) {
@@ -3272,19 +3176,19 @@ int CRoomsBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* n
     return GP_E_INVALID;
   }
   const CrDev dd = dev_for_launch();
-  const bool hansen = d.obs_kind == GP_OBS_HANSEN, staged = ctrl.lds_off >= 0;
+  const bool hansen = d.obs_kind == GP_OBS_HANSEN, staged = ctrl.dev.lds_off >= 0;
   timer.begin(s);
   if (hansen && staged)
-    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_HANSEN, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_HANSEN, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl.dev, K,
                        philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
   else if (hansen)
-    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_HANSEN, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_HANSEN, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl.dev, K,
                        philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
   else if (staged)
-    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_TABLE, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_TABLE, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl.dev, K,
                        philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
   else
-    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_TABLE, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl, K,
+    hipLaunchKernelGGL((crooms_rollout_ctrl<GP_OBS_TABLE, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, dd, ctrl.dev, K,
                        philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
   timer.end(s);
   philox_step += (uint64_t)K;

@@ -51,31 +51,6 @@ struct StDev {
   uint32_t* derr;
 };
 
-// A thread's 4 consecutive envs as one access (16 B of 4-byte elements, 4 B of flags) when all 4 are live and the
-// address is aligned to it; else element by element (the ragged tail, caller buffers off their boundary).
-__device__ __forceinline__ bool quad_ok(const void* base, int env0, int B, int esz) {
-  return env0 + 3 < B && ((((uintptr_t)base) + (size_t)env0 * esz) & (size_t)(4 * esz - 1)) == 0;
-}
-template <class T>
-__device__ __forceinline__ void load4(const T* b, int env0, int B, T (&v)[EPT]) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
-  if (quad_ok(b, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      const uint4 q = *reinterpret_cast<const uint4*>(b + env0);
-      const uint32_t w[EPT] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = __builtin_bit_cast(T, w[i]);
-    } else {
-      const uint32_t q = *reinterpret_cast<const uint32_t*>(b + env0);
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = (T)((q >> (8 * i)) & 0xFFu);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) v[i] = env0 + i < B ? b[env0 + i] : T(0);
-  }
-}
-
 // The planes' values of one step for a thread's 4 envs. o: the obs the choice was conditioned on (obs0 for step 0,
 // else the obs after step k - 1).
 struct Row {

@@ -1,5 +1,6 @@
 // gp_common.h — shared host/device helpers: 128-bit PCG64 arithmetic (numpy-compatible),
-// Philox4x32-10, status packing for the decoupled-lookback reset scan, error plumbing.
+// Philox4x32-10, status packing for the decoupled-lookback reset scan, the tile plumbing of the env kernels (metric
+// slots and their block reduction, StepOut, the 4-env quad accesses), error plumbing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -131,6 +132,110 @@ GP_HD uint64_t st_pack(uint64_t flag, uint32_t rej, uint32_t count) {
 GP_HD uint64_t st_flag(uint64_t s) { return s >> 62; }
 GP_HD uint32_t st_rej(uint64_t s) { return (uint32_t)(s >> 61) & 1u; }
 GP_HD uint32_t st_count(uint64_t s) { return (uint32_t)s; }
+
+// ---------------------------------------------------------------- tile plumbing of the env kernels ----
+// Per-block metric accumulators (each persistent block owns one slot); every kind's XxDev::mslot.
+struct alignas(32) MetricSlot {
+  double return_sum;
+  unsigned long long episodes, length_sum, env_steps;
+};
+// The sum of n slots as gp_metrics reports it: episodes, return, length, env-steps.
+inline void sum_metric_slots(const MetricSlot* m, size_t n, double out[4]) {
+  out[0] = out[1] = out[2] = out[3] = 0;
+  for (size_t i = 0; i < n; ++i) {
+    out[0] += (double)m[i].episodes;
+    out[1] += m[i].return_sum;
+    out[2] += (double)m[i].length_sum;
+    out[3] += (double)m[i].env_steps;
+  }
+}
+
+// What one env-step hands back to its rollout kernel.
+struct StepOut {
+  float rew;
+  uint8_t term, trunc;
+};
+
+// A block's metrics into its own slot p.mslot[blockIdx.x] (no other block writes it), p being the kind's XxDev: wave
+// shuffles, the waves' partials through LDS, thread 0 adds them up. LT: the type of the per-thread length sum
+// (Car-Flag's is 64-bit).
+template <int NW, class Dev, class LT>
+__device__ void block_metrics(const Dev& p, float rsum, uint32_t eps, LT lens, uint32_t nst) {
+  __shared__ float s_r[NW];
+  __shared__ uint32_t s_e[NW], s_n[NW];
+  __shared__ LT s_l[NW];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    rsum += __shfl_xor(rsum, d, 64);
+    eps += __shfl_xor(eps, d, 64);
+    lens += __shfl_xor(lens, d, 64);
+    nst += __shfl_xor(nst, d, 64);
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float r = 0.f;
+    unsigned long long e = 0, l = 0, n = 0;
+    for (int w = 0; w < NW; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
+    MetricSlot& m = p.mslot[blockIdx.x];
+    m.return_sum += (double)r;
+    m.episodes += e;
+    m.length_sum += l;
+    m.env_steps += n;
+  }
+}
+
+// A thread's 4 consecutive envs as one access (16 B of 4-byte elements, 8 B of 2-byte ones, 4 B of flags) when all 4
+// are live and the address is aligned to it; else element by element (the ragged tail, caller buffers off their
+// boundary): chosen per buffer and per step.
+__device__ __forceinline__ bool quad_ok(const void* p, int env0, int B, int esz) {
+  return env0 + 3 < B && ((((uintptr_t)p) + (size_t)env0 * esz) & (size_t)(4 * esz - 1)) == 0;
+}
+template <class T>
+__device__ __forceinline__ void load4(const T* __restrict__ p, int env0, int B, T (&v)[4]) {
+  if (quad_ok(p, env0, B, sizeof(T))) {
+    if constexpr (sizeof(T) == 4) {
+      uint4 q = *reinterpret_cast<const uint4*>(p + env0);
+      v[0] = __builtin_bit_cast(T, q.x); v[1] = __builtin_bit_cast(T, q.y);
+      v[2] = __builtin_bit_cast(T, q.z); v[3] = __builtin_bit_cast(T, q.w);
+    } else if constexpr (sizeof(T) == 2) {
+      uint2 q = *reinterpret_cast<const uint2*>(p + env0);
+      v[0] = (T)(q.x & 0xFFFF); v[1] = (T)(q.x >> 16); v[2] = (T)(q.y & 0xFFFF); v[3] = (T)(q.y >> 16);
+    } else {
+      uint32_t q = *reinterpret_cast<const uint32_t*>(p + env0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = (T)((q >> (8 * i)) & 0xFFu);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (env0 + i < B) ? p[env0 + i] : (T)0;
+  }
+}
+template <class T>
+__device__ __forceinline__ void store4(T* __restrict__ p, int env0, int B, const T (&v)[4]) {
+  if (quad_ok(p, env0, B, sizeof(T))) {
+    if constexpr (sizeof(T) == 4) {
+      uint4 q;
+      q.x = __builtin_bit_cast(uint32_t, v[0]); q.y = __builtin_bit_cast(uint32_t, v[1]);
+      q.z = __builtin_bit_cast(uint32_t, v[2]); q.w = __builtin_bit_cast(uint32_t, v[3]);
+      *reinterpret_cast<uint4*>(p + env0) = q;
+    } else if constexpr (sizeof(T) == 2) {
+      uint2 q;
+      q.x = (uint32_t)(uint16_t)v[0] | ((uint32_t)(uint16_t)v[1] << 16);
+      q.y = (uint32_t)(uint16_t)v[2] | ((uint32_t)(uint16_t)v[3] << 16);
+      *reinterpret_cast<uint2*>(p + env0) = q;
+    } else {
+      uint32_t q = (uint32_t)(uint8_t)v[0] | ((uint32_t)(uint8_t)v[1] << 8) | ((uint32_t)(uint8_t)v[2] << 16) |
+                   ((uint32_t)(uint8_t)v[3] << 24);
+      *reinterpret_cast<uint32_t*>(p + env0) = q;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (env0 + i < B) p[env0 + i] = v[i];
+  }
+}
 
 // ---------------------------------------------------------------- error plumbing ----
 // Per-handle device error word (GridCtl::err, the other kinds' `derr`): kernels OR bits into it,

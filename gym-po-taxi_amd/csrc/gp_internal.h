@@ -114,6 +114,9 @@ struct EnvBackend {
   // Closed-loop rollouts (gp_set_controller / gp_rollout_controller / gp_controller_nodes): GRID in philox mode,
   // ROCKSAMPLE, ANTTAG with the index obs in philox mode, TAXI with the Hansen obs in philox mode, HEAVENHELL,
   // CROOMS with a scalar obs and discrete actions in philox mode.
+  // What the six share lives in gp_ctrl.h (CtrlHost: install / clear, the LDS staging rule, the node plane, the
+  // rollout_controller precondition; the device helpers of the pick); a kind keeps its refusals, its kernels and
+  // the sizing of its closed-loop grid.
   virtual int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
     gp_set_error("controllers are not supported by this env kind");
     return GP_E_UNSUPPORTED;
@@ -127,7 +130,8 @@ struct EnvBackend {
     gp_set_error("controllers are not supported by this env kind");
     return GP_E_UNSUPPORTED;
   }
-  // Controller populations (gp_set_controller_population / gp_controller_scores): GRID only.
+  // Controller populations (gp_set_controller_population / gp_controller_scores): GRID only (CtrlHost::install with
+  // n_ctrl tables; the group checks, the weight table and the score slots are grid.hip's).
   virtual int set_controller_population(int n_ctrl, int64_t group_envs, int n_nodes, int n_obs, float gamma,
                                         const uint32_t* thr_host) {
     gp_set_error("controller populations are not supported by this env kind (GRID only)");
@@ -153,7 +157,7 @@ struct EnvBackend {
   }
   int stats_path = -1;  // the last gp_controller_stats launch: 1 = LDS histogram, 0 = global atomics (gp_query "stats_lds")
   virtual int valid_cells(int which, int32_t* out, int cap) const { return 0; }
-  virtual int metrics(double out[4]) = 0;
+  virtual int metrics(double out[4]) = 0;  // (the sum of the kind's MetricSlots: gp_common.h sum_metric_slots)
   // Syncs and reports device-side failures of earlier launches (GP_E_DEVICE); kinds without
   // cross-block waits have none.
   virtual int check() { return GP_OK; }

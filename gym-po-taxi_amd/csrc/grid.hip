@@ -137,53 +137,7 @@ __device__ __forceinline__ bool spin_give_up(const GridDev& p, uint32_t& spins) 
 }
 
 // ------------------------------------------------------------------ vector I/O helpers ----
-__device__ __forceinline__ bool full_aligned(const void* p, int env0, int B, int esz) {
-  return env0 + 3 < B && ((((uintptr_t)p) + (size_t)env0 * esz) & (size_t)(4 * esz - 1)) == 0;
-}
-template <class T>
-__device__ __forceinline__ void load4(const T* __restrict__ p, int env0, int B, T (&v)[4]) {
-  if (full_aligned(p, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      uint4 q = *reinterpret_cast<const uint4*>(p + env0);
-      v[0] = __builtin_bit_cast(T, q.x); v[1] = __builtin_bit_cast(T, q.y);
-      v[2] = __builtin_bit_cast(T, q.z); v[3] = __builtin_bit_cast(T, q.w);
-    } else if constexpr (sizeof(T) == 2) {
-      uint2 q = *reinterpret_cast<const uint2*>(p + env0);
-      v[0] = (T)(q.x & 0xFFFF); v[1] = (T)(q.x >> 16); v[2] = (T)(q.y & 0xFFFF); v[3] = (T)(q.y >> 16);
-    } else {
-      uint32_t q = *reinterpret_cast<const uint32_t*>(p + env0);
-      v[0] = (T)(q & 0xFF); v[1] = (T)((q >> 8) & 0xFF); v[2] = (T)((q >> 16) & 0xFF); v[3] = (T)(q >> 24);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (env0 + i < B) ? p[env0 + i] : (T)0;
-  }
-}
-template <class T>
-__device__ __forceinline__ void store4(T* __restrict__ p, int env0, int B, const T (&v)[4]) {
-  if (full_aligned(p, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      uint4 q;
-      q.x = __builtin_bit_cast(uint32_t, v[0]); q.y = __builtin_bit_cast(uint32_t, v[1]);
-      q.z = __builtin_bit_cast(uint32_t, v[2]); q.w = __builtin_bit_cast(uint32_t, v[3]);
-      *reinterpret_cast<uint4*>(p + env0) = q;
-    } else if constexpr (sizeof(T) == 2) {
-      uint2 q;
-      q.x = (uint32_t)(uint16_t)v[0] | ((uint32_t)(uint16_t)v[1] << 16);
-      q.y = (uint32_t)(uint16_t)v[2] | ((uint32_t)(uint16_t)v[3] << 16);
-      *reinterpret_cast<uint2*>(p + env0) = q;
-    } else {
-      uint32_t q = (uint32_t)(uint8_t)v[0] | ((uint32_t)(uint8_t)v[1] << 8) | ((uint32_t)(uint8_t)v[2] << 16) |
-                   ((uint32_t)(uint8_t)v[3] << 24);
-      *reinterpret_cast<uint32_t*>(p + env0) = q;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (env0 + i < B) p[env0 + i] = v[i];
-  }
-}
-
+// (quad_ok / load4 / store4: gp_common.h)
 // Fused-kernel variants: the host guarantees 16-B aligned base pointers (else the fused path is not
 // taken), so only the last, partial quad of a ragged batch takes the per-element path.
 template <class T>
@@ -2685,8 +2639,8 @@ __global__ __launch_bounds__(TPB) void grid_rollout_counter(GridDev p, int K, ui
 // state in registers. The row is read from global memory (L1/L2: ROOMS Hansen-8 tables are 74 KB-4.7 MB, FourRooms
 // Hansen-8 1.9 MB and up), or, CL, from a copy of the table staged in LDS behind the env's tables when both are small
 // (FourRooms Hansen-4: 6.5 KB with M = 1, 26 KB with M = 2). Rows are 16-B aligned: L = nact * M is a multiple of 4.
-// CTRL_TAG, CtrlDev, the row search ctrl_search and the staging budget CTRL_LDS_BUDGET: gp_ctrl.h (shared with
-// rocksample.hip, anttag.hip and taxi.hip). At that budget 5 blocks per CU stay resident, more than the 4 a 2^20-env
+// CTRL_TAG, CtrlDev, the pick (ctrl_pick over ctrl_search), ctrl_action / ctrl_node and the staging budget
+// CTRL_LDS_BUDGET: gp_ctrl.h (shared with the other five kinds). At that budget 5 blocks per CU stay resident, more than the 4 a 2^20-env
 // launch puts there.
 
 template <int OK, bool LT = false, bool CL = false>
@@ -2722,6 +2676,8 @@ __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDe
   int32_t ob[4];  // the obs of the state each env is in (what the previous step, or the reset, emitted)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
+    // (ctrl_clamp_node's rule in its own words: through the helper the error word's address, &p.ctl->err, is formed
+    // ahead of the branch and three instances of these kernels compile to other code)
     if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
       if (env0 + i < p.B) atomicOr(&p.ctl->err, GP_DERR_CTRL);
       nd[i] = (uint8_t)(c.M - 1);
@@ -2746,20 +2702,15 @@ __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDe
         philox_draws(p, env, step, k53, gi, ai);
         y = philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG, p.key0, p.key1).x[0] >> 1;
       }
-      uint32_t o = (uint32_t)ob[i];
-      if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
-        if (env < p.B) atomicOr(&p.ctl->err, GP_DERR_CTRL);
-        o = (uint32_t)c.n_obs - 1u;
-      }
-      const uint32_t* row = cthr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
-      const uint32_t j = min(ctrl_search(row, c.L, y), (uint32_t)c.L - 1u);
-      const uint32_t a = (j * c.inv_m) >> 16;  // j / M
+      const uint32_t j =
+          ctrl_pick(cthr, nd[i], c.n_obs, c.L, (uint32_t)c.L, (uint32_t)ob[i], y, env < p.B, &p.ctl->err);
+      const uint32_t a = ctrl_action(j, c.inv_m);
       n4[i] = nd[i];
       a4[i] = (int32_t)a;
       float r1 = 0.f;  // (the padding lanes of a ragged last block never enter the metrics: grid_rollout_counter)
       uint32_t e1 = 0, l1 = 0;
       counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], (int)a, k53, gi, ai, r[i], tm[i], tr[i], r1, e1, l1);
-      nd[i] = (tm[i] | tr[i]) ? (uint8_t)0 : (uint8_t)(j - a * (uint32_t)c.M);  // j % M; episode end: node 0
+      nd[i] = (tm[i] | tr[i]) ? (uint8_t)0 : (uint8_t)ctrl_node(j, a, c.M);  // episode end: node 0
       ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
       if (env < p.B) {
         rsum += r1;
@@ -2872,6 +2823,8 @@ __global__ __launch_bounds__(TPB) void grid_rollout_population(GridDev p, PopDev
   const float gamma = q.W[1];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
+    // (ctrl_clamp_node's rule in its own words: through the helper the error word's address, &p.ctl->err, is formed
+    // ahead of the branch and three instances of these kernels compile to other code)
     if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
       if (env0 + i < p.B) atomicOr(&p.ctl->err, GP_DERR_CTRL);
       nd[i] = (uint8_t)(c.M - 1);
@@ -2899,14 +2852,9 @@ __global__ __launch_bounds__(TPB) void grid_rollout_population(GridDev p, PopDev
         philox_draws(p, env, step, k53, gi, ai);
         y = philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG, p.key0, p.key1).x[0] >> 1;
       }
-      uint32_t o = (uint32_t)ob[i];
-      if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
-        if (live) atomicOr(&p.ctl->err, GP_DERR_CTRL);
-        o = (uint32_t)c.n_obs - 1u;
-      }
-      const uint32_t* row = cthr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
-      const uint32_t j = min(ctrl_search(row, c.L, y), (uint32_t)c.L - 1u);
-      const uint32_t a = (j * c.inv_m) >> 16;  // j / M
+      const uint32_t j =
+          ctrl_pick(cthr, nd[i], c.n_obs, c.L, (uint32_t)c.L, (uint32_t)ob[i], y, live, &p.ctl->err);
+      const uint32_t a = ctrl_action(j, c.inv_m);
       n4[i] = nd[i];
       a4[i] = (int32_t)a;
       float r1 = 0.f;  // (the padding lanes of a ragged last block enter neither the metrics nor the scores)
@@ -2923,7 +2871,7 @@ __global__ __launch_bounds__(TPB) void grid_rollout_population(GridDev p, PopDev
         gds += (double)dterm;
       }
       w4[i] = ended ? 1.0f : __fmul_rn(w4[i], gamma);
-      nd[i] = ended ? (uint8_t)0 : (uint8_t)(j - a * (uint32_t)c.M);  // j % M; episode end: node 0
+      nd[i] = ended ? (uint8_t)0 : (uint8_t)ctrl_node(j, a, c.M);  // episode end: node 0
       ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
     }
     if (act) store4<int32_t>(act + off, env0, p.B, a4);
@@ -3053,8 +3001,8 @@ struct GridBackend : EnvBackend {
     else if (!strcmp(key, "autotune_fused_ns")) *v = (int64_t)(at_ms[1] * 1e6f);
     // philox mode: the counter's step index of the next reset / step (what a restatement of the draws needs)
     else if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
-    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
-    else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.dev.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = ctrl.dev.M && ctrl.dev.lds_off >= 0;  // its table is staged in LDS
     else if (!strcmp(key, "controller_population")) *v = pop_P;  // controllers of the installed population (0 = none)
     else if (!strcmp(key, "controller_group_envs")) *v = pop_G;
     else if (!strcmp(key, "controller_group_multiple")) *v = EPB;  // group_envs must be a multiple of this
@@ -3095,10 +3043,9 @@ struct GridBackend : EnvBackend {
   int metrics(double out[4]) override;
   int autotune(int K, int reps, int* chosen) override;
   // closed-loop rollouts (grid_rollout_controller)
-  CtrlDev ctrl{};            // M == 0: no controller installed
-  DevBuf b_cthr, b_cnode;
+  CtrlHost ctrl;
   int controller_unsupported(const char* what) const;
-  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, d.nact, pop_P, pop_G, &d.ctl->err, out); }
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.dev.M, ctrl.dev.n_obs, d.nact, pop_P, pop_G, &d.ctl->err, out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override;
@@ -3494,13 +3441,7 @@ int GridBackend::metrics(double out[4]) {
   GP_HIP_CHECK(hipDeviceSynchronize());
   std::vector<MetricSlot> m(nslots);
   GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(MetricSlot) * nslots, hipMemcpyDeviceToHost));
-  out[0] = out[1] = out[2] = out[3] = 0;
-  for (const MetricSlot& x : m) {
-    out[0] += (double)x.episodes;
-    out[1] += x.return_sum;
-    out[2] += (double)x.length_sum;
-    out[3] += (double)x.env_steps;
-  }
+  sum_metric_slots(m.data(), m.size(), out);
   return check();
 }
 
@@ -3519,7 +3460,7 @@ static int dispatch_obs(int ok, F&& f) {
 
 int GridBackend::reset(void* obs, hipStream_t s) {
   GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * nslots, s));
-  if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
+  if (int e = ctrl.reset_nodes(B, s)) return e;
   if (pop_P) GP_HIP_CHECK(hipMemsetAsync(b_pslot.p, 0, sizeof(PopSlot) * (size_t)d.nblk, s));  // and every score
   const unsigned g1 = (unsigned)((B + TPB - 1) / TPB);
   const bool rgoal = d.fixed_goal < 0, ragent = d.fixed_agent < 0;
@@ -3758,62 +3699,35 @@ int GridBackend::controller_unsupported(const char* what) const {
 
 int GridBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
   if (int e = controller_unsupported("gp_set_controller")) return e;
-  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
   if (!thr_host) {
-    ctrl = CtrlDev{};
+    if (int e = ctrl.clear()) return e;
     drop_population();
-    int e;
-    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
     return GP_OK;
   }
-  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
-    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
-    return GP_E_INVALID;
-  }
-  const int L = d.nact * n_nodes;
-  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)L;
-  if (n > ((size_t)1 << 28)) {
-    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
-    return GP_E_INVALID;
-  }
-  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L)) return e;
-  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
-  drop_population();  // a single controller replaces a population
-  int e;
-  if ((e = b_cthr.alloc(n * sizeof(uint32_t))) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
-  GP_HIP_CHECK(hipMemcpy(b_cthr.p, thr_host, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  ctrl.thr = b_cthr.as<uint32_t>();
-  ctrl.node = b_cnode.as<uint8_t>();
-  ctrl.M = n_nodes;
-  ctrl.n_obs = n_obs;
-  ctrl.L = L;
-  ctrl.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
-  ctrl.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
+  const int e = ctrl.install("gp_set_controller", d.nact, n_nodes, n_obs, thr_host, B);
+  if (e == GP_E_INVALID) return e;  // a refused table: what was installed stays
+  drop_population();                // a single controller replaces a population (and a failed allocation leaves nothing)
+  if (e) return e;
   // Staged in LDS behind the env's tables when both fit CTRL_LDS_BUDGET per block (measured faster at
   // 6.5 and 26 KB tables); larger tables, and envs whose own tables are not in LDS, read the rows through the caches.
-  const int knob = gp_debug_knobs().ctrl_lds_max;
-  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
-  ctrl.lds_off = (d.lds.total > 0 && (size_t)d.lds.jt.off + n * sizeof(uint32_t) <= budget) ? d.lds.jt.off : -1;
+  ctrl.stage((size_t)d.lds.jt.off, d.lds.total > 0);
   return GP_OK;
 }
 
 int GridBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term,
                                     uint8_t* trunc, hipStream_t s) {
   if (int e = controller_unsupported("gp_rollout_controller")) return e;
-  if (!has_reset || !ctrl.M) {
-    gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
-                                                                      "(gp_set_controller)");
-    return GP_E_STATE;
-  }
+  if (int e = ctrl.ready(has_reset)) return e;
+  const CtrlDev& c = ctrl.dev;
   int e = dispatch_obs(d.obs_kind, [&](auto okc) -> int {
     constexpr int OK = decltype(okc)::value;
     if constexpr (OK == GP_OBS_HANSEN || OK == GP_OBS_TABLE) {
       timer.begin(s);
       if (pop_P) {  // a population: the same three table placements, per controller
-        const PopDev q{ctrl, pop_bpg, b_pw.as<float>(), b_pslot.as<PopSlot>()};
-        if (ctrl.lds_off >= 0)
+        const PopDev q{c, pop_bpg, b_pw.as<float>(), b_pslot.as<PopSlot>()};
+        if (c.lds_off >= 0)
           hipLaunchKernelGGL((grid_rollout_population<OK, true, true>), dim3(d.nblk), dim3(TPB),
-                             (size_t)ctrl.lds_off + (size_t)ctrl.bytes, s, d, q, K, philox_step, (int32_t*)obs, act,
+                             (size_t)c.lds_off + (size_t)c.bytes, s, d, q, K, philox_step, (int32_t*)obs, act,
                              nodes, rew, term, trunc);
         else if (d.lds.total > 0)
           hipLaunchKernelGGL((grid_rollout_population<OK, true>), dim3(d.nblk), dim3(TPB), (size_t)d.lds.jt.off, s, d,
@@ -3821,15 +3735,15 @@ int GridBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* nod
         else
           hipLaunchKernelGGL((grid_rollout_population<OK, false>), dim3(d.nblk), dim3(TPB), 0, s, d, q, K,
                              philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
-      } else if (ctrl.lds_off >= 0)  // the controller table staged behind the env's tables (set_controller decided)
+      } else if (c.lds_off >= 0)  // the controller table staged behind the env's tables (set_controller decided)
         hipLaunchKernelGGL((grid_rollout_controller<OK, true, true>), dim3(d.nblk), dim3(TPB),
-                           (size_t)ctrl.lds_off + (size_t)ctrl.bytes, s, d, ctrl, K, philox_step, (int32_t*)obs, act,
+                           (size_t)c.lds_off + (size_t)c.bytes, s, d, c, K, philox_step, (int32_t*)obs, act,
                            nodes, rew, term, trunc);
       else if (d.lds.total > 0)  // the env's tables in LDS, as gp_rollout has them
         hipLaunchKernelGGL((grid_rollout_controller<OK, true>), dim3(d.nblk), dim3(TPB), (size_t)d.lds.jt.off, s, d,
-                           ctrl, K, philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
+                           c, K, philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
       else
-        hipLaunchKernelGGL((grid_rollout_controller<OK, false>), dim3(d.nblk), dim3(TPB), 0, s, d, ctrl, K,
+        hipLaunchKernelGGL((grid_rollout_controller<OK, false>), dim3(d.nblk), dim3(TPB), 0, s, d, c, K,
                            philox_step, (int32_t*)obs, act, nodes, rew, term, trunc);
       timer.end(s);
     }
@@ -3843,13 +3757,7 @@ int GridBackend::rollout_controller(int K, void* obs, int32_t* act, uint8_t* nod
 
 int GridBackend::controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) {
   if (int e = controller_unsupported("gp_controller_nodes")) return e;
-  if (!ctrl.M) {
-    gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
-    return GP_E_STATE;
-  }
-  if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
-  if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
-  return GP_OK;
+  return ctrl.nodes(get, set, B, s);
 }
 
 // ---- controller populations ----
@@ -3858,11 +3766,7 @@ int GridBackend::set_controller_population(int n_ctrl, int64_t group_envs, int n
   if (int e = controller_unsupported("gp_set_controller_population")) return e;
   if (!thr_host) return set_controller(0, 0, nullptr);  // removes whichever is installed
   GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the tables being replaced)
-  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
-    gp_set_error("gp_set_controller_population: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)",
-                 n_nodes, n_obs);
-    return GP_E_INVALID;
-  }
+  if (int e = CtrlHost::check_range("gp_set_controller_population", n_nodes, n_obs)) return e;
   if (group_envs < EPB || group_envs % EPB) {
     gp_set_error("gp_set_controller_population: group_envs must be a positive multiple of %d, the envs of one rollout "
                  "block (got %lld)", EPB, (long long)group_envs);
@@ -3878,42 +3782,29 @@ int GridBackend::set_controller_population(int n_ctrl, int64_t group_envs, int n
     gp_set_error("gp_set_controller_population: gamma must be in (0, 1] (got %g)", (double)gamma);
     return GP_E_INVALID;
   }
-  const int L = d.nact * n_nodes;
-  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n1 = rows * (size_t)L, n = n1 * (size_t)n_ctrl;
-  if (n > ((size_t)1 << 28)) {
-    gp_set_error("gp_set_controller_population: tables of %zu entries in total are too large (max 2^28)", n);
-    return GP_E_INVALID;
-  }
-  for (int c = 0; c < n_ctrl; ++c)
-    if (int e = ctrl_validate_rows(thr_host + (size_t)c * n1, rows, n_obs, L)) {
-      const std::string row_error = gp_last_error();  // names the node and obs
-      gp_set_error("gp_set_controller_population: controller %d: %s", c, row_error.c_str());
-      return e;
-    }
   std::vector<float> W(65536);
   float w = 1.0f;
   for (float& x : W) {  // sequential float32 products, one rounding each (a product alone cannot contract)
     x = w;
     w = w * gamma;
   }
-  ctrl = CtrlDev{};  // (nothing installed if an allocation below fails)
-  drop_population();
-  int e;
-  if ((e = b_cthr.alloc(n * sizeof(uint32_t))) || (e = b_cnode.alloc((size_t)B + 16)) ||  // nodes zeroed
-      (e = b_pw.upload(W)) || (e = b_pslot.alloc(sizeof(PopSlot) * (size_t)d.nblk)))      // scores zeroed
+  // the tables [P][M][n_obs][L]; ctrl.dev then describes ONE controller (bytes, and the staging rule of
+  // set_controller on one table: a block stages only its own)
+  int e = ctrl.install("gp_set_controller_population", d.nact, n_nodes, n_obs, thr_host, B, n_ctrl);
+  if (e == GP_E_INVALID) {  // what was installed stays
+    if (ctrl.bad_ctrl >= 0) {
+      const std::string row_error = gp_last_error();  // names the node and obs
+      gp_set_error("gp_set_controller_population: controller %d: %s", ctrl.bad_ctrl, row_error.c_str());
+    }
     return e;
-  GP_HIP_CHECK(hipMemcpy(b_cthr.p, thr_host, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  ctrl.thr = b_cthr.as<uint32_t>();
-  ctrl.node = b_cnode.as<uint8_t>();
-  ctrl.M = n_nodes;
-  ctrl.n_obs = n_obs;
-  ctrl.L = L;
-  ctrl.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
-  ctrl.bytes = (int32_t)std::min(n1 * sizeof(uint32_t), (size_t)INT32_MAX);
-  // the staging rule of set_controller on ONE controller's table: a block stages only its own
-  const int knob = gp_debug_knobs().ctrl_lds_max;
-  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
-  ctrl.lds_off = (d.lds.total > 0 && (size_t)d.lds.jt.off + n1 * sizeof(uint32_t) <= budget) ? d.lds.jt.off : -1;
+  }
+  drop_population();
+  if (e) return e;
+  if ((e = b_pw.upload(W)) || (e = b_pslot.alloc(sizeof(PopSlot) * (size_t)d.nblk))) {  // scores zeroed
+    ctrl.dev = CtrlDev{};  // (nothing installed if an allocation fails)
+    return e;
+  }
+  ctrl.stage((size_t)d.lds.jt.off, d.lds.total > 0);
   pop_P = n_ctrl;
   pop_G = group_envs;
   pop_bpg = (int)std::min<int64_t>(group_envs / EPB, d.nblk);

@@ -1,6 +1,6 @@
 // grid_shared.h — device-side structures shared by the GRID backend (grid.hip) and the windowed numpy-exact
-// rollout (wgrid.hip): the numpy-mode control block, the per-block metric slots, and the windowed kernel's
-// parameter block. Not part of the C ABI.
+// rollout (wgrid.hip): the numpy-mode control block and the windowed kernel's parameter block (the per-block metric
+// slots, MetricSlot, are every kind's: gp_common.h). Not part of the C ABI.
 #pragma once
 #include "gp_common.h"
 
@@ -15,12 +15,6 @@ struct alignas(64) GridCtl {
                                         //   advance it, so its steps stay contiguous when windowed launches interleave)
   uint32_t fb_last;                     // fused kernels: resets b of the last step (next launch's window centre)
   uint32_t wstep;                       // windowed kernel: its own steps taken (its granule tags)
-};
-
-// Per-block metric accumulators (each persistent block owns one slot).
-struct alignas(32) MetricSlot {
-  double return_sum;
-  unsigned long long episodes, length_sum, env_steps;
 };
 
 // ---------------------------------------------------------------- windowed fused rollout (wgrid.hip) ----

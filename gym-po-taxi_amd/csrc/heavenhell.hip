@@ -54,11 +54,6 @@ constexpr uint32_t TAG = 0x6868656cu;  // 'hhel'
 constexpr uint32_t F_FREE = 1u, F_LEFT = 2u, F_RIGHT = 4u, F_PRIEST = 8u, F_START = 16u;
 constexpr uint32_t F_ALL = 31u, TOP = 1u << 31;
 
-struct alignas(32) HhSlot {
-  double return_sum;
-  unsigned long long episodes, length_sum, env_steps;
-};
-
 struct HhDev {
   int32_t B, ntiles, W, H, ncells, n_start;
   uint32_t divm;      // ceil(2^16 / W): cell / W == (cell * divm) >> 16 for cells < 256
@@ -69,7 +64,7 @@ struct HhDev {
   const uint8_t* tabs;  // [ncells] flags | [ncells] obs base | [n_start] start cells ascending; each padded to 16 B
   int32_t off_base, off_start, tab_bytes;
   uint32_t* st;  // [B] cell | side << 8 | elapsed << 16
-  HhSlot* mslot;
+  MetricSlot* mslot;
   uint32_t* derr;  // device error word (GP_DERR_*)
 };
 
@@ -88,11 +83,6 @@ __device__ __forceinline__ uint32_t hh_reset_word(const HhDev& p, const uint8_t*
   const uint32_t si = (uint32_t)(((uint64_t)x2 * (uint32_t)p.n_start) >> 32);
   return (uint32_t)tabs[p.off_start + si] | ((x3 & 1u) << 8);
 }
-
-struct StepOut {
-  float rew;
-  uint8_t term, trunc;
-};
 
 __device__ __forceinline__ StepOut hh_env_step(const HhDev& p, const uint8_t* lds, uint32_t& st, int a, int env,
                                                bool live, uint64_t step, float& rsum, uint32_t& eps, uint32_t& lens) {
@@ -146,74 +136,6 @@ __device__ __forceinline__ StepOut hh_env_step(const HhDev& p, const uint8_t* ld
   return o;
 }
 
-__device__ void hh_metrics(const HhDev& p, float rsum, uint32_t eps, uint32_t lens, uint32_t nst) {
-  __shared__ float s_r[WAVES];
-  __shared__ uint32_t s_e[WAVES], s_l[WAVES], s_n[WAVES];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
-  __syncthreads();
-  if (threadIdx.x == 0) {  // the block's own slot: no other block writes it
-    float r = 0.f;
-    unsigned long long e = 0, l = 0, n = 0;
-    for (int w = 0; w < WAVES; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
-    HhSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
-    m.episodes += e;
-    m.length_sum += l;
-    m.env_steps += n;
-  }
-}
-
-// A thread's 4 consecutive envs as one access (16 B of 4-byte elements, 4 B of flags) when all 4 are live and the
-// address is aligned to it; else element by element (the ragged tail, caller buffers off their boundary).
-__device__ __forceinline__ bool quad_ok(const void* base, int env0, int B, int esz) {
-  return env0 + 3 < B && ((((uintptr_t)base) + (size_t)env0 * esz) & (size_t)(4 * esz - 1)) == 0;
-}
-template <class T>
-__device__ __forceinline__ void load4(const T* b, int env0, int B, T (&v)[EPT]) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
-  if (quad_ok(b, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      const uint4 q = *reinterpret_cast<const uint4*>(b + env0);
-      const uint32_t w[EPT] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = __builtin_bit_cast(T, w[i]);
-    } else {
-      const uint32_t q = *reinterpret_cast<const uint32_t*>(b + env0);
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = (T)((q >> (8 * i)) & 0xFFu);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) v[i] = env0 + i < B ? b[env0 + i] : T(0);
-  }
-}
-template <class T>
-__device__ __forceinline__ void store4(T* b, int env0, int B, const T (&v)[EPT]) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
-  if (quad_ok(b, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<uint4*>(b + env0) =
-          make_uint4(__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
-                     __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3]));
-    } else {
-      *reinterpret_cast<uint32_t*>(b + env0) =
-          (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i)
-      if (env0 + i < B) b[env0 + i] = v[i];
-  }
-}
-
 // K steps of every env. CTRL = false: the actions come from `act` [K, B], loaded one step ahead. CTRL = true
 // (gp_rollout_controller): each action is drawn by the installed controller from the env's obs and node (gp_ctrl.h);
 // `aout` / `nodes` receive the actions and nodes. CL: the controller table is staged in the dynamic LDS behind the
@@ -252,10 +174,7 @@ __global__ __launch_bounds__(TPB) void hh_rollout(HhDev p, CtrlDev c, int K, uin
       load4<uint8_t>(c.node, env0, p.B, nd);
 #pragma unroll
       for (int i = 0; i < EPT; ++i) {
-        if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
-          if (env0 + i < p.B) atomicOr(p.derr, GP_DERR_CTRL);
-          nd[i] = (uint8_t)(c.M - 1);
-        }
+        ctrl_clamp_node(nd[i], c.M, env0 + i < p.B, p.derr);
         ob[i] = hh_obs(p, lds, st[i]);
       }
     } else {
@@ -272,14 +191,8 @@ __global__ __launch_bounds__(TPB) void hh_rollout(HhDev p, CtrlDev c, int K, uin
         for (int i = 0; i < EPT; ++i) {
           const int env = env0 + i;
           const uint32_t y = env < p.B ? hh_block(p, env, step, CTRL_TAG).x[0] >> 1 : 0u;
-          uint32_t o = (uint32_t)ob[i];
-          if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
-            if (env < p.B) atomicOr(p.derr, GP_DERR_CTRL);
-            o = (uint32_t)c.n_obs - 1u;
-          }
-          const uint32_t* row = cthr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
-          jj[i] = min(ctrl_search(row, c.L, y), (uint32_t)c.L - 1u);  // (< L by the row's last entry, 2^31 > y)
-          a[i] = (int32_t)((jj[i] * c.inv_m) >> 16);                  // j / M
+          jj[i] = ctrl_pick(cthr, nd[i], c.n_obs, c.L, (uint32_t)c.L, (uint32_t)ob[i], y, env < p.B, p.derr);
+          a[i] = (int32_t)ctrl_action(jj[i], c.inv_m);
           n4[i] = nd[i];
         }
       } else {
@@ -298,8 +211,8 @@ __global__ __launch_bounds__(TPB) void hh_rollout(HhDev p, CtrlDev c, int K, uin
         tr[i] = o.trunc;
         ob[i] = hh_obs(p, lds, st[i]);
         nst += live ? 1u : 0u;
-        if constexpr (CTRL)  // j % M; episode end: node 0
-          nd[i] = (o.term | o.trunc) ? (uint8_t)0 : (uint8_t)(jj[i] - (uint32_t)a[i] * (uint32_t)c.M);
+        if constexpr (CTRL)  // episode end: node 0
+          nd[i] = (o.term | o.trunc) ? (uint8_t)0 : (uint8_t)ctrl_node(jj[i], (uint32_t)a[i], c.M);
       }
       if constexpr (CTRL) {
         if (aout) store4<int32_t>(aout + off, env0, p.B, a);
@@ -313,7 +226,7 @@ __global__ __launch_bounds__(TPB) void hh_rollout(HhDev p, CtrlDev c, int K, uin
     store4<uint32_t>(p.st, env0, p.B, st);
     if constexpr (CTRL) store4<uint8_t>(c.node, env0, p.B, nd);
   }
-  hh_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 __global__ __launch_bounds__(TPB) void hh_reset(HhDev p, uint64_t step, int32_t* __restrict__ obs) {
@@ -348,11 +261,11 @@ __global__ void hh_set_state(HhDev p, const int32_t* agent, const int32_t* side,
 // ------------------------------------------------------------------ host backend ----
 struct HeavenHellBackend : EnvBackend {
   HhDev d{};
-  CtrlDev ctrl{};  // M == 0: no controller installed
+  CtrlHost ctrl;
   int grid = 1, grid_ctrl = 1, cus = 1;
   size_t lds_ctrl = 0;  // dynamic LDS of the closed-loop launches
   uint64_t philox_step = 0;
-  DevBuf b_tabs, b_st, b_slot, b_cthr, b_cnode;
+  DevBuf b_tabs, b_st, b_slot;
   DevErr derr;
 
   int build(const gp_heavenhell_config* cfg);
@@ -374,14 +287,14 @@ struct HeavenHellBackend : EnvBackend {
   }
   int query(const char* key, int64_t* v) const override {
     if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
-    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
-    else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.dev.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = ctrl.dev.M && ctrl.dev.lds_off >= 0;  // its table is staged in LDS
     else return EnvBackend::query(key, v);
     return GP_OK;
   }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(HhSlot) * grid, s));
-    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * grid, s));
+    if (int e = ctrl.reset_nodes(B, s)) return e;
     const unsigned nb = (unsigned)std::min<int64_t>((B + TPB - 1) / TPB, 65536);
     hipLaunchKernelGGL(hh_reset, dim3(nb), dim3(TPB), 0, s, d, philox_step, (int32_t*)obs);
     ++philox_step;
@@ -419,99 +332,46 @@ struct HeavenHellBackend : EnvBackend {
     has_reset = true;
     return GP_OK;
   }
-  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, NACT, 0, 0, derr.ptr(), out); }
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.dev.M, ctrl.dev.n_obs, NACT, 0, 0, derr.ptr(), out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override {
-    if (!has_reset || !ctrl.M) {
-      gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
-                                                                        "(gp_set_controller)");
-      return GP_E_STATE;
-    }
+    if (int e = ctrl.ready(has_reset)) return e;
     timer.begin(s);
-    if (ctrl.lds_off >= 0)
-      hipLaunchKernelGGL((hh_rollout<true, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, d, ctrl, K, philox_step,
+    if (ctrl.dev.lds_off >= 0)
+      hipLaunchKernelGGL((hh_rollout<true, true>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, d, ctrl.dev, K, philox_step,
                          (const int32_t*)nullptr, (int32_t*)obs, act, nodes, rew, term, trunc);
     else
-      hipLaunchKernelGGL((hh_rollout<true, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, d, ctrl, K, philox_step,
+      hipLaunchKernelGGL((hh_rollout<true, false>), dim3(grid_ctrl), dim3(TPB), lds_ctrl, s, d, ctrl.dev, K, philox_step,
                          (const int32_t*)nullptr, (int32_t*)obs, act, nodes, rew, term, trunc);
     timer.end(s);
     philox_step += (uint64_t)K;
     GP_HIP_CHECK(hipGetLastError());
     return GP_OK;
   }
-  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
-    if (!ctrl.M) {
-      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
-      return GP_E_STATE;
-    }
-    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
-    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
-    return GP_OK;
-  }
+  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override { return ctrl.nodes(get, set, B, s); }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<HhSlot> m(grid);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(HhSlot) * grid, hipMemcpyDeviceToHost));
-    out[0] = out[1] = out[2] = out[3] = 0;
-    for (const HhSlot& x : m) {
-      out[0] += (double)x.episodes;
-      out[1] += x.return_sum;
-      out[2] += (double)x.length_sum;
-      out[3] += (double)x.env_steps;
-    }
+    std::vector<MetricSlot> m(grid);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(MetricSlot) * grid, hipMemcpyDeviceToHost));
+    sum_metric_slots(m.data(), m.size(), out);
     return check();
   }
 };
 
-// thr_host rows hold L = 4 M entries (M <= 8: L <= 32, below the 64 up to which j / M by inv_m is exact): whole 16-B
-// quads, uploaded as they are. The table is staged in LDS behind the env's tables when both fit CTRL_LDS_BUDGET (knob
-// ctrl_lds_max, at most 60 KB: with the 64 B of static LDS a launch stays below 64 KB); the closed-loop grid is sized
-// from the kernel's occupancy at that dynamic-LDS size and never exceeds the open loop's (one set of metric slots).
+// A = 4: rows of whole 16-B quads. The closed-loop grid is sized from the kernel's occupancy at the launch's
+// dynamic-LDS size (CtrlHost::stage) and never exceeds the open loop's (one set of metric slots).
 int HeavenHellBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
-  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
-  if (!thr_host) {
-    ctrl = CtrlDev{};
-    int e;
-    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
-    return GP_OK;
-  }
-  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
-    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
-    return GP_E_INVALID;
-  }
-  const int L = NACT * n_nodes;
-  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)L;
-  if (n > ((size_t)1 << 28)) {
-    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
-    return GP_E_INVALID;
-  }
-  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L)) return e;
-  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
-  std::vector<uint32_t> host(thr_host, thr_host + n);
-  int e;
-  if ((e = b_cthr.upload(host)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
-  CtrlDev c{};
-  c.thr = b_cthr.as<uint32_t>();
-  c.node = b_cnode.as<uint8_t>();
-  c.M = n_nodes;
-  c.n_obs = n_obs;
-  c.L = L;
-  c.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
-  c.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
-  const int knob = gp_debug_knobs().ctrl_lds_max;
-  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
-  const bool staged = (size_t)d.tab_bytes + n * sizeof(uint32_t) <= budget;
-  c.lds_off = staged ? d.tab_bytes : -1;
-  lds_ctrl = (size_t)d.tab_bytes + (staged ? n * sizeof(uint32_t) : 0);
+  if (!thr_host) return ctrl.clear();
+  if (int e = ctrl.install("gp_set_controller", NACT, n_nodes, n_obs, thr_host, B)) return e;
+  lds_ctrl = ctrl.stage((size_t)d.tab_bytes, true);
   int occ = 0;
-  if (staged) {
-    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hh_rollout<true, true>, TPB, lds_ctrl));
-  } else {
-    GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hh_rollout<true, false>, TPB, lds_ctrl));
-  }
+  const hipError_t he =
+      ctrl.dev.lds_off >= 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hh_rollout<true, true>, TPB, lds_ctrl)
+                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hh_rollout<true, false>, TPB, lds_ctrl);
+  if (he != hipSuccess) ctrl.dev = CtrlDev{};  // (no controller, as after a failed allocation)
+  GP_HIP_CHECK(he);
   grid_ctrl = std::min(persistent_grid(d.ntiles, cus, occ), grid);
-  ctrl = c;
   return GP_OK;
 }
 
@@ -600,8 +460,8 @@ int HeavenHellBackend::build(const gp_heavenhell_config* cfg) {
   grid_ctrl = grid;
   persist_grid = grid;
   persist_occ = occ;
-  if ((e = b_slot.alloc(sizeof(HhSlot) * grid))) return e;
-  d.mslot = b_slot.as<HhSlot>();
+  if ((e = b_slot.alloc(sizeof(MetricSlot) * grid))) return e;
+  d.mslot = b_slot.as<MetricSlot>();
   if ((e = derr.alloc())) return e;
   d.derr = derr.ptr();
   return GP_OK;

@@ -48,12 +48,6 @@ constexpr int MAX_ROCKS = 16;  // the good mask fits 16 bits
 constexpr int NMOVE = 4, A_SAMPLE = 4, A_CHECK = 5;
 constexpr uint32_t TAG = 0x726f636bu;  // 'rock'
 constexpr uint8_t NO_ROCK = 0xFF;
-constexpr int CTRL_MAX_L = 64;  // A * M: j / M by the 16-bit magic multiply is exact for j < 64
-
-struct alignas(32) RsSlot {
-  double return_sum;
-  unsigned long long episodes, length_sum, env_steps;
-};
 
 struct RsDev {
   int32_t B, ntiles, W, H, k, ncells, A;
@@ -66,7 +60,7 @@ struct RsDev {
   int32_t off_rock, tab_bytes;
   uint32_t* cm;  // [B] cell | mask << 8 | last reading << 24
   uint32_t* el;  // [B] elapsed
-  RsSlot* mslot;
+  MetricSlot* mslot;
   uint32_t* derr;  // device error word (GP_DERR_*)
 };
 
@@ -84,11 +78,6 @@ __device__ __forceinline__ int32_t rs_obs(const RsDev& p, uint32_t cm) {
   const int32_t reading = (int32_t)(cm >> 24);
   return p.obs_cell ? (int32_t)(cm & 0xFFu) * 3 + reading : reading;
 }
-
-struct StepOut {
-  float rew;
-  uint8_t term, trunc;
-};
 
 __device__ __forceinline__ StepOut rs_env_step(const RsDev& p, const uint8_t* lds, uint32_t& cm, uint32_t& el, int a,
                                                int env, bool live, uint64_t step, float& rsum, uint32_t& eps,
@@ -149,74 +138,6 @@ __device__ __forceinline__ StepOut rs_env_step(const RsDev& p, const uint8_t* ld
   return o;
 }
 
-__device__ void rs_metrics(const RsDev& p, float rsum, uint32_t eps, uint32_t lens, uint32_t nst) {
-  __shared__ float s_r[WAVES];
-  __shared__ uint32_t s_e[WAVES], s_l[WAVES], s_n[WAVES];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float r = 0.f;
-    unsigned long long e = 0, l = 0, n = 0;
-    for (int w = 0; w < WAVES; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
-    RsSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
-    m.episodes += e;
-    m.length_sum += l;
-    m.env_steps += n;
-  }
-}
-
-// A thread's 4 consecutive envs as one access (16 B of 4-byte elements, 4 B of flags) when all 4 are live and the
-// address is aligned to it; else element by element (the ragged tail, caller buffers off their boundary).
-__device__ __forceinline__ bool quad_ok(const void* base, int env0, int B, int esz) {
-  return env0 + 3 < B && ((((uintptr_t)base) + (size_t)env0 * esz) & (size_t)(4 * esz - 1)) == 0;
-}
-template <class T>
-__device__ __forceinline__ void load4(const T* b, int env0, int B, T (&v)[EPT]) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
-  if (quad_ok(b, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      const uint4 q = *reinterpret_cast<const uint4*>(b + env0);
-      const uint32_t w[EPT] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = __builtin_bit_cast(T, w[i]);
-    } else {
-      const uint32_t q = *reinterpret_cast<const uint32_t*>(b + env0);
-#pragma unroll
-      for (int i = 0; i < EPT; ++i) v[i] = (T)((q >> (8 * i)) & 0xFFu);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) v[i] = env0 + i < B ? b[env0 + i] : T(0);
-  }
-}
-template <class T>
-__device__ __forceinline__ void store4(T* b, int env0, int B, const T (&v)[EPT]) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "4-byte elements or byte flags");
-  if (quad_ok(b, env0, B, sizeof(T))) {
-    if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<uint4*>(b + env0) =
-          make_uint4(__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
-                     __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3]));
-    } else {
-      *reinterpret_cast<uint32_t*>(b + env0) =
-          (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i)
-      if (env0 + i < B) b[env0 + i] = v[i];
-  }
-}
-
 // K steps of every env: a persistent grid-stride loop over 1,024-env tiles, 4 consecutive envs per thread with their
 // state in registers across the K steps. CTRL = false: the actions come from `act` [K, B], loaded one step ahead.
 // CTRL = true (gp_rollout_controller): each action is drawn by the installed controller from the env's obs and node
@@ -244,10 +165,7 @@ __global__ __launch_bounds__(TPB) void rs_rollout(RsDev p, CtrlDev c, int K, uin
       load4<uint8_t>(c.node, env0, p.B, nd);
 #pragma unroll
       for (int i = 0; i < EPT; ++i)
-        if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
-          if (env0 + i < p.B) atomicOr(p.derr, GP_DERR_CTRL);
-          nd[i] = (uint8_t)(c.M - 1);
-        }
+        ctrl_clamp_node(nd[i], c.M, env0 + i < p.B, p.derr);
     } else {
       if (K > 0) load4<int32_t>(act, env0, p.B, a_nxt);
     }
@@ -263,14 +181,8 @@ __global__ __launch_bounds__(TPB) void rs_rollout(RsDev p, CtrlDev c, int K, uin
         for (int i = 0; i < EPT; ++i) {
           const int env = env0 + i;
           const uint32_t y = env < p.B ? rs_block(p, env, step, CTRL_TAG).x[0] >> 1 : 0u;
-          uint32_t o = (uint32_t)rs_obs(p, cm[i]);
-          if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
-            if (env < p.B) atomicOr(p.derr, GP_DERR_CTRL);
-            o = (uint32_t)c.n_obs - 1u;
-          }
-          const uint32_t* row = c.thr + ((size_t)nd[i] * (size_t)c.n_obs + o) * (size_t)c.L;
-          jj[i] = min(ctrl_search(row, c.L, y), lreal - 1u);
-          a[i] = (int32_t)((jj[i] * c.inv_m) >> 16);  // j / M
+          jj[i] = ctrl_pick(c.thr, nd[i], c.n_obs, c.L, lreal, (uint32_t)rs_obs(p, cm[i]), y, env < p.B, p.derr);
+          a[i] = (int32_t)ctrl_action(jj[i], c.inv_m);
           n4[i] = nd[i];
         }
       } else {
@@ -290,8 +202,8 @@ __global__ __launch_bounds__(TPB) void rs_rollout(RsDev p, CtrlDev c, int K, uin
         tr[i] = o.trunc;
         ob[i] = rs_obs(p, cm[i]);
         nst += live ? 1u : 0u;
-        if constexpr (CTRL)  // j % M; episode end: node 0
-          nd[i] = (o.term | o.trunc) ? (uint8_t)0 : (uint8_t)(jj[i] - (uint32_t)a[i] * (uint32_t)c.M);
+        if constexpr (CTRL)  // episode end: node 0
+          nd[i] = (o.term | o.trunc) ? (uint8_t)0 : (uint8_t)ctrl_node(jj[i], (uint32_t)a[i], c.M);
       }
       if constexpr (CTRL) {
         if (aout) store4<int32_t>(aout + off, env0, p.B, a);
@@ -306,7 +218,7 @@ __global__ __launch_bounds__(TPB) void rs_rollout(RsDev p, CtrlDev c, int K, uin
     store4<uint32_t>(p.el, env0, p.B, el);
     if constexpr (CTRL) store4<uint8_t>(c.node, env0, p.B, nd);
   }
-  rs_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 __global__ __launch_bounds__(TPB) void rs_reset(RsDev p, uint64_t step, int32_t* __restrict__ obs) {
@@ -340,10 +252,10 @@ __global__ void rs_set_state(RsDev p, const int32_t* agent, const int32_t* rocks
 // ------------------------------------------------------------------ host backend ----
 struct RockSampleBackend : EnvBackend {
   RsDev d{};
-  CtrlDev ctrl{};  // M == 0: no controller installed
+  CtrlHost ctrl;
   int grid = 1;
   uint64_t philox_step = 0;
-  DevBuf b_tabs, b_cm, b_el, b_slot, b_cthr, b_cnode;
+  DevBuf b_tabs, b_cm, b_el, b_slot;
   DevErr derr;
 
   int build(const gp_rocksample_config* cfg);
@@ -365,14 +277,14 @@ struct RockSampleBackend : EnvBackend {
   }
   int query(const char* key, int64_t* v) const override {
     if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
-    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.dev.M;  // node count of the installed controller (0 = none)
     else if (!strcmp(key, "controller_lds")) *v = 0;         // the table is read from global memory
     else return EnvBackend::query(key, v);
     return GP_OK;
   }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(RsSlot) * grid, s));
-    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * grid, s));
+    if (int e = ctrl.reset_nodes(B, s)) return e;
     const unsigned nb = (unsigned)std::min<int64_t>((B + TPB - 1) / TPB, 65536);
     hipLaunchKernelGGL(rs_reset, dim3(nb), dim3(TPB), 0, s, d, philox_step, (int32_t*)obs);
     ++philox_step;
@@ -409,86 +321,33 @@ struct RockSampleBackend : EnvBackend {
     has_reset = true;
     return GP_OK;
   }
-  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, d.A, 0, 0, derr.ptr(), out); }
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.dev.M, ctrl.dev.n_obs, d.A, 0, 0, derr.ptr(), out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override {
-    if (!has_reset || !ctrl.M) {
-      gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
-                                                                        "(gp_set_controller)");
-      return GP_E_STATE;
-    }
+    if (int e = ctrl.ready(has_reset)) return e;
     timer.begin(s);
-    hipLaunchKernelGGL(rs_rollout<true>, dim3(grid), dim3(TPB), d.tab_bytes, s, d, ctrl, K, philox_step,
+    hipLaunchKernelGGL(rs_rollout<true>, dim3(grid), dim3(TPB), d.tab_bytes, s, d, ctrl.dev, K, philox_step,
                        (const int32_t*)nullptr, (int32_t*)obs, act, nodes, rew, term, trunc);
     timer.end(s);
     philox_step += (uint64_t)K;
     GP_HIP_CHECK(hipGetLastError());
     return GP_OK;
   }
-  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
-    if (!ctrl.M) {
-      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
-      return GP_E_STATE;
-    }
-    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
-    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
-    return GP_OK;
-  }
+  int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override { return ctrl.nodes(get, set, B, s); }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<RsSlot> m(grid);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(RsSlot) * grid, hipMemcpyDeviceToHost));
-    out[0] = out[1] = out[2] = out[3] = 0;
-    for (const RsSlot& x : m) {
-      out[0] += (double)x.episodes;
-      out[1] += x.return_sum;
-      out[2] += (double)x.length_sum;
-      out[3] += (double)x.env_steps;
-    }
+    std::vector<MetricSlot> m(grid);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(MetricSlot) * grid, hipMemcpyDeviceToHost));
+    sum_metric_slots(m.data(), m.size(), out);
     return check();
   }
 };
 
-// thr_host rows hold L = A * M entries; A = 5 + k is no multiple of 4 in general, so each uploaded row is padded to
-// a multiple of 4 entries with 2^31 (never counted: y < 2^31) and ctrl_search keeps its 16-B quads.
+// A = 5 + k is no multiple of 4 in general: CtrlHost::install pads the rows. The table is read from global memory.
 int RockSampleBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
-  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
-  if (!thr_host) {
-    ctrl = CtrlDev{};
-    int e;
-    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
-    return GP_OK;
-  }
-  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
-    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
-    return GP_E_INVALID;
-  }
-  const int L = d.A * n_nodes, Lp = (L + 3) & ~3;
-  if (L > CTRL_MAX_L) {
-    gp_set_error("gp_set_controller: %d actions x %d nodes = %d joint choices, more than %d", d.A, n_nodes, L,
-                 CTRL_MAX_L);
-    return GP_E_INVALID;
-  }
-  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)Lp;
-  if (n > ((size_t)1 << 28)) {
-    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
-    return GP_E_INVALID;
-  }
-  std::vector<uint32_t> padded(n);
-  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L, Lp, padded.data())) return e;
-  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
-  int e;
-  if ((e = b_cthr.upload(padded)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
-  ctrl.thr = b_cthr.as<uint32_t>();
-  ctrl.node = b_cnode.as<uint8_t>();
-  ctrl.M = n_nodes;
-  ctrl.n_obs = n_obs;
-  ctrl.L = Lp;
-  ctrl.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
-  ctrl.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
-  ctrl.lds_off = -1;
-  return GP_OK;
+  if (!thr_host) return ctrl.clear();
+  return ctrl.install("gp_set_controller", d.A, n_nodes, n_obs, thr_host, B);
 }
 
 int RockSampleBackend::build(const gp_rocksample_config* cfg) {
@@ -574,8 +433,8 @@ int RockSampleBackend::build(const gp_rocksample_config* cfg) {
   grid = persistent_grid(d.ntiles, prop.multiProcessorCount, occ);
   persist_grid = grid;
   persist_occ = occ;
-  if ((e = b_slot.alloc(sizeof(RsSlot) * grid))) return e;
-  d.mslot = b_slot.as<RsSlot>();
+  if ((e = b_slot.alloc(sizeof(MetricSlot) * grid))) return e;
+  d.mslot = b_slot.as<MetricSlot>();
   if ((e = derr.alloc())) return e;
   d.derr = derr.ptr();
   return GP_OK;

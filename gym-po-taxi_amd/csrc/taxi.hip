@@ -45,11 +45,6 @@ constexpr int TCOL = NACT + 1;  // transition-table columns: the 5 actions + the
 constexpr int MAX_NS = 4096;    // s fits 12 bits of the packed state
 constexpr uint32_t PHILOX_TAG = 0x74617869u;  // 'taxi'
 
-struct alignas(32) TaxiSlot {
-  double return_sum;
-  unsigned long long episodes, length_sum, env_steps;
-};
-
 struct TaxiDev {
   int32_t B, ntiles;
   int32_t ns, nlocs, lpl;          // lpl = L*(L+1): states per taxi cell
@@ -60,7 +55,7 @@ struct TaxiDev {
   const uint8_t* tabs;             // packed tables (global), staged into LDS
   int32_t off_trans, off_obs, off_cdf, off_valid, tab_bytes;
   uint32_t* st;                    // [B] s | nd << 12 | elapsed << 16
-  TaxiSlot* mslot;                 // [grid]
+  MetricSlot* mslot;                // [grid]
   uint32_t* derr;                  // device error word (GP_DERR_*)
   const int32_t* rp_state;         // replay: reset state per env (GP_RNG_REPLAY)
   const int32_t* rp_pd;            // replay: p*L + d per env
@@ -123,11 +118,6 @@ __device__ __forceinline__ uint32_t draw_pd(const TaxiDev& p, int env, uint64_t 
   }
 }
 
-struct StepOut {
-  float rew;
-  uint8_t term, trunc;
-};
-
 // One env-step of TaxiVecEnv.step (extended_taxi.py:244-287) on the packed state `u`.
 template <bool REPLAY>
 __device__ __forceinline__ StepOut taxi_env_step(const TaxiDev& p, const uint8_t* lds, uint32_t& u, int a, int env,
@@ -165,38 +155,7 @@ __device__ __forceinline__ StepOut taxi_env_step(const TaxiDev& p, const uint8_t
   return o;
 }
 
-// ---- vector I/O (4 consecutive envs per thread) ----
-__device__ __forceinline__ bool quad_ok(const void* base, int env0, int B, int esz) {
-  return env0 + 3 < B && ((((uintptr_t)base) + (size_t)env0 * esz) & (size_t)(4 * esz - 1)) == 0;
-}
-__device__ __forceinline__ void ld4_u32(const uint32_t* __restrict__ p, int env0, int B, uint32_t (&v)[4]) {
-  if (quad_ok(p, env0, B, 4)) {
-    const uint4 q = *reinterpret_cast<const uint4*>(p + env0);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = env0 + i < B ? p[env0 + i] : 0u;
-  }
-}
-__device__ __forceinline__ void st4_u32(uint32_t* __restrict__ p, int env0, int B, const uint32_t (&v)[4]) {
-  if (quad_ok(p, env0, B, 4)) {
-    *reinterpret_cast<uint4*>(p + env0) = make_uint4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (env0 + i < B) p[env0 + i] = v[i];
-  }
-}
-__device__ __forceinline__ void st4_u8(uint8_t* __restrict__ p, int env0, int B, const uint8_t (&v)[4]) {
-  if (quad_ok(p, env0, B, 1)) {
-    *reinterpret_cast<uint32_t*>(p + env0) =
-        (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (env0 + i < B) p[env0 + i] = v[i];
-  }
-}
+// (vector I/O, 4 consecutive envs per thread: quad_ok / load4 / store4 of gp_common.h)
 
 // ---- one-hot rows as a wave-contiguous chunk stream ----
 // The wave owns envs [e0, e0 + n) (lane l holds envs 4l..4l+3), i.e. the byte range
@@ -240,33 +199,6 @@ __device__ __forceinline__ void write_onehot_wave(uint8_t* __restrict__ out, int
   __builtin_amdgcn_wave_barrier();  // hs is rewritten by the next step
 }
 
-// Per-block metrics into the block's own slot (the grid is persistent: block b owns slot b).
-template <int NW = WAVES>
-__device__ void taxi_metrics(const TaxiDev& p, float rsum, uint32_t eps, uint32_t lens, uint32_t nst) {
-  __shared__ float s_r[NW];
-  __shared__ uint32_t s_e[NW], s_l[NW], s_n[NW];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float r = 0.f;
-    unsigned long long e = 0, l = 0, n = 0;
-    for (int w = 0; w < NW; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
-    TaxiSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
-    m.episodes += e;
-    m.length_sum += l;
-    m.env_steps += n;
-  }
-}
-
 // ---- the rollout kernel: K steps for every env, persistent over 1024-env tiles ----
 // OH = 0: scalar int32 obs [K,B]; OH = CS in {16, 4, 1}: one-hot uint8 [K,B,n_obs] in CS-byte chunks.
 template <int OH, bool REPLAY>
@@ -284,11 +216,11 @@ __global__ __launch_bounds__(TPB) void taxi_rollout(TaxiDev p, int K, uint64_t s
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;
     uint32_t u[4];
-    ld4_u32(p.st, env0, p.B, u);
+    load4<uint32_t>(p.st, env0, p.B, u);
     for (int k = 0; k < K; ++k) {
       const size_t off = (size_t)k * p.B;
       uint32_t a4[4];
-      ld4_u32(reinterpret_cast<const uint32_t*>(act + off), env0, p.B, a4);
+      load4<uint32_t>(reinterpret_cast<const uint32_t*>(act + off), env0, p.B, a4);
       float r[4];
       uint8_t tm[4], tr[4];
       uint32_t h[4];
@@ -303,12 +235,11 @@ __global__ __launch_bounds__(TPB) void taxi_rollout(TaxiDev p, int K, uint64_t s
         h[i] = obs_of[u[i] & 0xFFFu];
         nst += live ? 1u : 0u;
       }
-      st4_u32(reinterpret_cast<uint32_t*>(rew + off), env0, p.B,
-              {__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])});
-      st4_u8(term + off, env0, p.B, tm);
-      st4_u8(trunc + off, env0, p.B, tr);
+      store4<float>(rew + off, env0, p.B, r);
+      store4<uint8_t>(term + off, env0, p.B, tm);
+      store4<uint8_t>(trunc + off, env0, p.B, tr);
       if constexpr (OH == 0) {
-        st4_u32(reinterpret_cast<uint32_t*>(obs) + off, env0, p.B, h);
+        store4<uint32_t>(reinterpret_cast<uint32_t*>(obs) + off, env0, p.B, h);
       } else {
         const int we0 = tile * EPB + wid * 256;  // first env of this wave
         const int n = min(256, p.B - we0);
@@ -317,9 +248,9 @@ __global__ __launch_bounds__(TPB) void taxi_rollout(TaxiDev p, int K, uint64_t s
                                 lane);
       }
     }
-    st4_u32(p.st, env0, p.B, u);
+    store4<uint32_t>(p.st, env0, p.B, u);
   }
-  taxi_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 // ---- the closed-loop rollout: taxi_rollout<OH, false> with the action drawn on the device ----
@@ -355,7 +286,8 @@ __global__ __launch_bounds__(TPB) void taxi_rollout_ctrl(TaxiDev p, CtrlDev c, i
     const int env0 = tile * EPB + threadIdx.x * EPT;
     uint32_t u[4], h[4];
     uint8_t nd[4];
-    ld4_u32(p.st, env0, p.B, u);
+    load4<uint32_t>(p.st, env0, p.B, u);
+    // (the node quad in its own words, here and at the tile's end: load4 / store4<uint8_t> compile to other code)
     const bool nq = quad_ok(c.node, env0, p.B, 1);
     if (nq) {
       const uint32_t q = *reinterpret_cast<const uint32_t*>(c.node + env0);
@@ -367,10 +299,7 @@ __global__ __launch_bounds__(TPB) void taxi_rollout_ctrl(TaxiDev p, CtrlDev c, i
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if (nd[i] >= c.M) {  // (only through gp_controller_nodes: clamped so that the row stays inside the table)
-        if (env0 + i < p.B) atomicOr(p.derr, GP_DERR_CTRL);
-        nd[i] = (uint8_t)(c.M - 1);
-      }
+      ctrl_clamp_node(nd[i], c.M, env0 + i < p.B, p.derr);
       h[i] = obs_of[u[i] & 0xFFFu];  // the obs of the state the env is in (what the reset, or the last step, emitted)
     }
     for (int k = 0; k < K; ++k) {
@@ -386,35 +315,28 @@ __global__ __launch_bounds__(TPB) void taxi_rollout_ctrl(TaxiDev p, CtrlDev c, i
         const uint32_t y = live ? philox4x32_10((uint32_t)env, (uint32_t)step, (uint32_t)(step >> 32), CTRL_TAG, p.key0,
                                                 p.key1).x[0] >> 1
                                 : 0u;
-        uint32_t o = h[i];
-        if (o >= (uint32_t)c.n_obs) {  // a table smaller than the obs space: flagged, clamped (in bounds)
-          if (live) atomicOr(p.derr, GP_DERR_CTRL);
-          o = (uint32_t)c.n_obs - 1u;
-        }
         // (a table holds at most 2^28 entries: the entry index fits 32 bits)
-        const uint32_t* row = cthr + ((uint32_t)nd[i] * (uint32_t)c.n_obs + o) * (uint32_t)c.L;
-        const uint32_t j = min(ctrl_search(row, c.L, y), lreal - 1u);  // never a padding entry
-        const uint32_t a = (j * c.inv_m) >> 16;                         // j / M
+        const uint32_t j = ctrl_pick<uint32_t>(cthr, nd[i], c.n_obs, c.L, lreal, h[i], y, live, p.derr);
+        const uint32_t a = ctrl_action(j, c.inv_m);
         n4[i] = nd[i];
         a4[i] = a;
         const StepOut so = taxi_env_step<false>(p, lds, u[i], (int)a, env, live, step, rsum, eps, lens);
         r[i] = so.rew;
         tm[i] = so.term;
         tr[i] = so.trunc;
-        nd[i] = (so.term | so.trunc) ? (uint8_t)0 : (uint8_t)(j - a * (uint32_t)c.M);  // j % M; episode end: node 0
+        nd[i] = (so.term | so.trunc) ? (uint8_t)0 : (uint8_t)ctrl_node(j, a, c.M);  // episode end: node 0
         h[i] = obs_of[u[i] & 0xFFFu];
         nst += live ? 1u : 0u;
       }
-      if (act) st4_u32(reinterpret_cast<uint32_t*>(act + off), env0, p.B, a4);
-      if (nodes) st4_u8(nodes + off, env0, p.B, n4);
+      if (act) store4<uint32_t>(reinterpret_cast<uint32_t*>(act + off), env0, p.B, a4);
+      if (nodes) store4<uint8_t>(nodes + off, env0, p.B, n4);
       if (rew)
-        st4_u32(reinterpret_cast<uint32_t*>(rew + off), env0, p.B,
-                {__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])});
-      if (term) st4_u8(term + off, env0, p.B, tm);
-      if (trunc) st4_u8(trunc + off, env0, p.B, tr);
+        store4<float>(rew + off, env0, p.B, r);
+      if (term) store4<uint8_t>(term + off, env0, p.B, tm);
+      if (trunc) store4<uint8_t>(trunc + off, env0, p.B, tr);
       if (obs) {
         if constexpr (OH == 0) {
-          st4_u32(reinterpret_cast<uint32_t*>(obs) + off, env0, p.B, h);
+          store4<uint32_t>(reinterpret_cast<uint32_t*>(obs) + off, env0, p.B, h);
         } else {
           const int we0 = tile * EPB + wid * 256;  // first env of this wave
           const int n = min(256, p.B - we0);
@@ -424,7 +346,7 @@ __global__ __launch_bounds__(TPB) void taxi_rollout_ctrl(TaxiDev p, CtrlDev c, i
         }
       }
     }
-    st4_u32(p.st, env0, p.B, u);
+    store4<uint32_t>(p.st, env0, p.B, u);
     if (nq) {
       *reinterpret_cast<uint32_t*>(c.node + env0) =
           (uint32_t)nd[0] | ((uint32_t)nd[1] << 8) | ((uint32_t)nd[2] << 16) | ((uint32_t)nd[3] << 24);
@@ -434,7 +356,7 @@ __global__ __launch_bounds__(TPB) void taxi_rollout_ctrl(TaxiDev p, CtrlDev c, i
         if (env0 + i < p.B) c.node[env0 + i] = nd[i];
     }
   }
-  taxi_metrics(p, rsum, eps, lens, nst);
+  block_metrics<WAVES>(p, rsum, eps, lens, nst);
 }
 
 // reset(): every env draws a start state (extended_taxi.py:232-242); one step index of the stream.
@@ -454,9 +376,9 @@ __global__ __launch_bounds__(TPB) void taxi_reset(TaxiDev p, uint64_t step, void
       u[i] = env < p.B ? draw_reset<REPLAY>(p, lds, env, step) : 0u;
       h[i] = l_obs(lds, p)[u[i]];
     }
-    st4_u32(p.st, env0, p.B, u);
+    store4<uint32_t>(p.st, env0, p.B, u);
     if constexpr (OH == 0) {
-      st4_u32(reinterpret_cast<uint32_t*>(obs), env0, p.B, h);
+      store4<uint32_t>(reinterpret_cast<uint32_t*>(obs), env0, p.B, h);
     } else {
       const int we0 = tile * EPB + wid * 256;
       const int n = min(256, p.B - we0);
@@ -1024,7 +946,7 @@ __global__ __launch_bounds__(NP_TPB) void taxi_np_kernel(TaxiDev p, TaxiNpDev q,
     q.rng[4] = sh.has;
     q.rng[5] = sh.uval;
   }
-  if (K > 0) taxi_metrics<NP_WAVES>(p, rsum, eps, lens, nst);
+  if (K > 0) block_metrics<NP_WAVES>(p, rsum, eps, lens, nst);
 }
 
 // ---- numpy mode, grid-wide (B > NPG_MIN_ENVS): the same step as three launches ----
@@ -1089,7 +1011,7 @@ __device__ void npg_metrics(const TaxiDev& p, int slots, float rsum, uint32_t ep
     float r = 0.f;
     unsigned long long e = 0, l = 0, n = 0;
     for (int w = 0; w < WAVES; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
-    TaxiSlot& m = p.mslot[blockIdx.x % (unsigned)slots];
+    MetricSlot& m = p.mslot[blockIdx.x % (unsigned)slots];
     atomicAdd(&m.return_sum, (double)r);
     atomicAdd(&m.episodes, e);
     atomicAdd(&m.length_sum, l);
@@ -1117,8 +1039,8 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass1(TaxiDev p, TaxiNpDev q, Np
     }
   } else {
     uint32_t u[4], a4[4];
-    ld4_u32(p.st, env0, p.B, u);
-    ld4_u32(reinterpret_cast<const uint32_t*>(act + off), env0, p.B, a4);
+    load4<uint32_t>(p.st, env0, p.B, u);
+    load4<uint32_t>(reinterpret_cast<const uint32_t*>(act + off), env0, p.B, a4);
     float r[4];
     uint8_t tm[4], tr[4];
 #pragma unroll
@@ -1150,11 +1072,12 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass1(TaxiDev p, TaxiNpDev q, Np
       }
       u[i] = s | (min(nd, 15u) << 12) | (min(el, 0xFFFFu) << 16);  // nd saturates (as taxi_env_step)
     }
-    st4_u32(reinterpret_cast<uint32_t*>(rew + off), env0, p.B,
-            {__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])});
-    st4_u8(term + off, env0, p.B, tm);
-    st4_u8(trunc + off, env0, p.B, tr);
-    st4_u32(p.st, env0, p.B, u);
+    // (the rewards as words: store4<float> of r compiles this kernel to other code)
+    store4<uint32_t>(reinterpret_cast<uint32_t*>(rew + off), env0, p.B,
+                     {__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])});
+    store4<uint8_t>(term + off, env0, p.B, tm);
+    store4<uint8_t>(trunc + off, env0, p.B, tr);
+    store4<uint32_t>(p.st, env0, p.B, u);
   }
   // ranks in env order within the tile (env0 + i: thread-major, then i)
   uint32_t ctc = 0, crs = 0;
@@ -1173,7 +1096,7 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass1(TaxiDev p, TaxiNpDev q, Np
     rtc += ftc[i] ? 1u : 0u;
     rrs += frs[i] ? 1u : 0u;
   }
-  st4_u32(reinterpret_cast<uint32_t*>(q.rk), env0, p.B,
+  store4<uint32_t>(reinterpret_cast<uint32_t*>(q.rk), env0, p.B,
           {(uint32_t)rk[0], (uint32_t)rk[1], (uint32_t)rk[2], (uint32_t)rk[3]});
   if (threadIdx.x == 0) g.bcnt[tile] = (uint32_t)tot | ((uint32_t)(tot >> 32) << 16);
   if (!RESET) npg_metrics(p, g.grid, rsum, eps, lens, nst);
@@ -1408,8 +1331,8 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass2(TaxiDev p, TaxiNpDev q, Np
   const uint64_t pre = g.bpre[tile];
   const uint32_t ptc = (uint32_t)pre, prs = (uint32_t)(pre >> 32);
   uint32_t u[4], rk[4], h[4];
-  ld4_u32(p.st, env0, p.B, u);
-  ld4_u32(reinterpret_cast<const uint32_t*>(q.rk), env0, p.B, rk);
+  load4<uint32_t>(p.st, env0, p.B, u);
+  load4<uint32_t>(reinterpret_cast<const uint32_t*>(q.rk), env0, p.B, rk);
   const uint16_t* obs_of = l_obs(lds, p);
 #pragma unroll
   for (int i = 0; i < EPT; ++i) {
@@ -1427,9 +1350,9 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass2(TaxiDev p, TaxiNpDev q, Np
     }
     h[i] = obs_of[u[i] & 0xFFFu];
   }
-  st4_u32(p.st, env0, p.B, u);
+  store4<uint32_t>(p.st, env0, p.B, u);
   if constexpr (OH == 0) {
-    st4_u32(reinterpret_cast<uint32_t*>(obs) + off, env0, p.B, h);
+    store4<uint32_t>(reinterpret_cast<uint32_t*>(obs) + off, env0, p.B, h);
   } else {
     const int we0 = tile * EPB + wid * 256;
     const int n = min(256, p.B - we0);
@@ -1447,10 +1370,10 @@ struct TaxiBackend : EnvBackend {
   int cus = 1, bpc_knob = 0;    // CUs of the device; the persist_bpc knob as gp_create read it
   int one_hot = 0;
   bool hansen_obs = false;      // obs_kind == GP_OBS_HANSEN (the obs closed-loop rollouts condition on)
-  CtrlDev ctrl{};               // M == 0: no controller installed
+  CtrlHost ctrl;
   uint64_t philox_step = 0;
   std::vector<double> law;      // P(start state = valid[k])
-  DevBuf b_tabs, b_st, b_slot, b_cthr, b_cnode;
+  DevBuf b_tabs, b_st, b_slot;
   DevErr derr;
   const int32_t* rp_state = nullptr;
   const int32_t* rp_pd = nullptr;
@@ -1489,9 +1412,9 @@ struct TaxiBackend : EnvBackend {
   int check() override { return derr.check("taxi"); }
   int query(const char* key, int64_t* v) const override {
     if (!strcmp(key, "philox_step")) *v = (int64_t)philox_step;
-    else if (!strcmp(key, "controller_nodes")) *v = ctrl.M;  // node count of the installed controller (0 = none)
-    else if (!strcmp(key, "controller_lds")) *v = ctrl.M && ctrl.lds_off >= 0;  // its table is staged in LDS
-    else if (!strcmp(key, "controller_blocks")) *v = ctrl.M ? grid_ctrl : 0;    // blocks of the closed-loop rollout
+    else if (!strcmp(key, "controller_nodes")) *v = ctrl.dev.M;  // node count of the installed controller (0 = none)
+    else if (!strcmp(key, "controller_lds")) *v = ctrl.dev.M && ctrl.dev.lds_off >= 0;  // its table is staged in LDS
+    else if (!strcmp(key, "controller_blocks")) *v = ctrl.dev.M ? grid_ctrl : 0;    // blocks of the closed-loop rollout
     else return EnvBackend::query(key, v);
     return GP_OK;
   }
@@ -1511,37 +1434,33 @@ struct TaxiBackend : EnvBackend {
     }
     return GP_OK;
   }
-  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.M, ctrl.n_obs, NACT, 0, 0, derr.ptr(), out); }
+  int controller_shape(CtrlShape* out) const override { return ctrl_shape_of(ctrl.dev.M, ctrl.dev.n_obs, NACT, 0, 0, derr.ptr(), out); }
   int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) override;
   template <bool CL>
   void launch_ctrl(int cs, int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                    hipStream_t s) {
     const dim3 g((unsigned)grid_ctrl), b(TPB);
-    const size_t lds = (size_t)d.tab_bytes + (CL ? (size_t)ctrl.bytes : 0);
+    const size_t lds = (size_t)d.tab_bytes + (CL ? (size_t)ctrl.dev.bytes : 0);
     if (!one_hot)
-      hipLaunchKernelGGL((taxi_rollout_ctrl<0, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+      hipLaunchKernelGGL((taxi_rollout_ctrl<0, CL>), g, b, lds, s, d, ctrl.dev, K, philox_step, obs, act, nodes, rew, term,
                          trunc);
     else if (cs == 16)
-      hipLaunchKernelGGL((taxi_rollout_ctrl<16, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+      hipLaunchKernelGGL((taxi_rollout_ctrl<16, CL>), g, b, lds, s, d, ctrl.dev, K, philox_step, obs, act, nodes, rew, term,
                          trunc);
     else if (cs == 4)
-      hipLaunchKernelGGL((taxi_rollout_ctrl<4, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+      hipLaunchKernelGGL((taxi_rollout_ctrl<4, CL>), g, b, lds, s, d, ctrl.dev, K, philox_step, obs, act, nodes, rew, term,
                          trunc);
     else
-      hipLaunchKernelGGL((taxi_rollout_ctrl<1, CL>), g, b, lds, s, d, ctrl, K, philox_step, obs, act, nodes, rew, term,
+      hipLaunchKernelGGL((taxi_rollout_ctrl<1, CL>), g, b, lds, s, d, ctrl.dev, K, philox_step, obs, act, nodes, rew, term,
                          trunc);
   }
   int rollout_controller(int K, void* obs, int32_t* act, uint8_t* nodes, float* rew, uint8_t* term, uint8_t* trunc,
                          hipStream_t s) override {
     if (int e = ctrl_supported("gp_rollout_controller")) return e;
-    if (!has_reset || !ctrl.M) {
-      gp_set_error(!has_reset ? "rollout_controller() before reset()" : "rollout_controller() without a controller "
-                                                                        "(gp_set_controller)");
-      return GP_E_STATE;
-    }
+    if (int e = ctrl.ready(has_reset)) return e;
     const int cs = one_hot && obs ? chunk_size(obs, K) : 16;  // (no obs plane: no one-hot stream runs)
     timer.begin(s);
-    if (ctrl.lds_off >= 0) launch_ctrl<true>(cs, K, obs, act, nodes, rew, term, trunc, s);
+    if (ctrl.dev.lds_off >= 0) launch_ctrl<true>(cs, K, obs, act, nodes, rew, term, trunc, s);
     else launch_ctrl<false>(cs, K, obs, act, nodes, rew, term, trunc, s);
     timer.end(s);
     GP_HIP_CHECK(hipGetLastError());
@@ -1550,13 +1469,7 @@ struct TaxiBackend : EnvBackend {
   }
   int controller_nodes(uint8_t* get, const uint8_t* set, hipStream_t s) override {
     if (int e = ctrl_supported("gp_controller_nodes")) return e;
-    if (!ctrl.M) {
-      gp_set_error("gp_controller_nodes without a controller (gp_set_controller)");
-      return GP_E_STATE;
-    }
-    if (get) GP_HIP_CHECK(hipMemcpyAsync(get, ctrl.node, (size_t)B, hipMemcpyDeviceToDevice, s));
-    if (set) GP_HIP_CHECK(hipMemcpyAsync(ctrl.node, set, (size_t)B, hipMemcpyDeviceToDevice, s));
-    return GP_OK;
+    return ctrl.nodes(get, set, B, s);
   }
   int set_rng_state(const RngHost& r) override {
     if (rng_mode != GP_RNG_NUMPY) {
@@ -1666,8 +1579,8 @@ struct TaxiBackend : EnvBackend {
     else hipLaunchKernelGGL((taxi_reset<1, REPLAY>), g, b, lds, s, dd, step, obs);
   }
   int reset(void* obs, hipStream_t s) override {
-    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(TaxiSlot) * nslot, s));
-    if (ctrl.M) GP_HIP_CHECK(hipMemsetAsync(ctrl.node, 0, (size_t)B, s));  // every controller node back to 0
+    GP_HIP_CHECK(hipMemsetAsync(d.mslot, 0, sizeof(MetricSlot) * nslot, s));
+    if (int e = ctrl.reset_nodes(B, s)) return e;
     const int cs = chunk_size(obs, 1);
     if (rng_mode == GP_RNG_NUMPY) {
       launch_np(0, nullptr, obs, nullptr, nullptr, nullptr, s);
@@ -1734,15 +1647,9 @@ struct TaxiBackend : EnvBackend {
   }
   int metrics(double out[4]) override {
     GP_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<TaxiSlot> m(nslot);
-    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(TaxiSlot) * nslot, hipMemcpyDeviceToHost));
-    out[0] = out[1] = out[2] = out[3] = 0;
-    for (const TaxiSlot& x : m) {
-      out[0] += (double)x.episodes;
-      out[1] += x.return_sum;
-      out[2] += (double)x.length_sum;
-      out[3] += (double)x.env_steps;
-    }
+    std::vector<MetricSlot> m(nslot);
+    GP_HIP_CHECK(hipMemcpy(m.data(), d.mslot, sizeof(MetricSlot) * nslot, hipMemcpyDeviceToHost));
+    sum_metric_slots(m.data(), m.size(), out);
     return check();
   }
   int reset_distribution(double* out, int cap) const override {
@@ -1938,8 +1845,8 @@ int TaxiBackend::build(const gp_taxi_config* cfg) {
   bpc_knob = gp_debug_knobs().persist_bpc;
   hansen_obs = cfg->obs_kind == GP_OBS_HANSEN;
   nslot = std::max(grid, std::max(1, std::min((int)d.ntiles, cus * (bpc_knob > 0 ? bpc_knob : 8))));
-  if (int e = b_slot.alloc(sizeof(TaxiSlot) * nslot)) return e;
-  d.mslot = b_slot.as<TaxiSlot>();
+  if (int e = b_slot.alloc(sizeof(MetricSlot) * nslot)) return e;
+  d.mslot = b_slot.as<MetricSlot>();
   if (int e = derr.alloc()) return e;
   d.derr = derr.ptr();
   if (d.tab_bytes > 64 * 1024) {
@@ -1951,56 +1858,23 @@ int TaxiBackend::build(const gp_taxi_config* cfg) {
   return GP_OK;
 }
 
-// thr_host rows hold L = 5 M entries (M <= 8: L <= 40, below the 64 up to which j / M by inv_m is exact); L is no
-// multiple of 4 in general, so each uploaded row is padded to a multiple of 4 entries with 2^31 (never counted:
-// y < 2^31) and ctrl_search keeps its 16-B quads. The table is staged in LDS behind the env's tables when both fit
-// CTRL_LDS_BUDGET (knob ctrl_lds_max, at most 60 KB: with the 2 KB of static LDS a launch stays below 64 KB), and the
-// closed-loop kernel's persistent grid is sized from its occupancy at that dynamic-LDS size.
+// L = 5 M is no multiple of 4 in general: CtrlHost::install pads the rows. The closed-loop kernel's persistent grid is
+// sized from its occupancy at the launch's dynamic-LDS size (CtrlHost::stage).
 int TaxiBackend::set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
   if (int e = ctrl_supported("gp_set_controller")) return e;
-  GP_HIP_CHECK(hipDeviceSynchronize());  // (an earlier launch may still read the table being replaced)
-  if (!thr_host) {
-    ctrl = CtrlDev{};
-    int e;
-    if ((e = b_cthr.alloc(0)) || (e = b_cnode.alloc(0))) return e;
-    return GP_OK;
-  }
-  if (n_nodes < 1 || n_nodes > 8 || n_obs < 1 || n_obs > (1 << 24)) {
-    gp_set_error("gp_set_controller: n_nodes must be in [1, 8] and n_obs in [1, 2^24] (got %d, %d)", n_nodes, n_obs);
-    return GP_E_INVALID;
-  }
-  const int L = NACT * n_nodes, Lp = (L + 3) & ~3;
-  const size_t rows = (size_t)n_nodes * (size_t)n_obs, n = rows * (size_t)Lp;
-  if (n > ((size_t)1 << 28)) {
-    gp_set_error("gp_set_controller: a table of %zu entries is too large (max 2^28)", n);
-    return GP_E_INVALID;
-  }
-  std::vector<uint32_t> padded(n);
-  if (int e = ctrl_validate_rows(thr_host, rows, n_obs, L, Lp, padded.data())) return e;
-  ctrl = CtrlDev{};  // (no controller if an allocation below fails)
-  int e;
-  if ((e = b_cthr.upload(padded)) || (e = b_cnode.alloc((size_t)B + 16))) return e;  // nodes zeroed
-  CtrlDev c{};
-  c.thr = b_cthr.as<uint32_t>();
-  c.node = b_cnode.as<uint8_t>();
-  c.M = n_nodes;
-  c.n_obs = n_obs;
-  c.L = Lp;
-  c.inv_m = (65536u + (uint32_t)n_nodes - 1u) / (uint32_t)n_nodes;
-  c.bytes = (int32_t)std::min(n * sizeof(uint32_t), (size_t)INT32_MAX);
-  const int knob = gp_debug_knobs().ctrl_lds_max;
-  const size_t budget = knob >= 0 ? std::min((size_t)knob, (size_t)60 * 1024) : (size_t)CTRL_LDS_BUDGET;
-  const bool staged = (size_t)d.tab_bytes + n * sizeof(uint32_t) <= budget;
-  c.lds_off = staged ? d.tab_bytes : -1;
-  const size_t lds = (size_t)d.tab_bytes + (staged ? n * sizeof(uint32_t) : 0);
+  if (!thr_host) return ctrl.clear();
+  if (int e = ctrl.install("gp_set_controller", NACT, n_nodes, n_obs, thr_host, B)) return e;
+  const size_t lds = ctrl.stage((size_t)d.tab_bytes, true);
+  const bool staged = ctrl.dev.lds_off >= 0;
   int occ = 0;
   using Kern = void (*)(TaxiDev, CtrlDev, int, uint64_t, void*, int32_t*, uint8_t*, float*, uint8_t*, uint8_t*);
   const Kern kern = staged ? (one_hot ? taxi_rollout_ctrl<16, true> : taxi_rollout_ctrl<0, true>)
                            : (one_hot ? taxi_rollout_ctrl<16, false> : taxi_rollout_ctrl<0, false>);
-  GP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, TPB, lds));
+  const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, TPB, lds);
+  if (he != hipSuccess) ctrl.dev = CtrlDev{};  // (no controller, as after a failed allocation)
+  GP_HIP_CHECK(he);
   const int bpc = bpc_knob > 0 ? bpc_knob : std::min(std::max(occ, 1), 8);  // as persistent_grid, the knob as created
   grid_ctrl = std::max(1, std::min(std::min((int)d.ntiles, cus * bpc), nslot));  // never past the metric slots
-  ctrl = c;
   return GP_OK;
 }
 
