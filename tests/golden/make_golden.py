@@ -86,6 +86,10 @@ CASES = {
     "taxi_2pass_hansen": (TX, dict(hansen_obs=True, num_passengers=2, time_limit=400), 128, 800, 3, 34, True),
     "taxi_ext_3pass_rew": (TX, dict(map="EXTENDED", num_passengers=3, time_limit=300, reward_goal=2.0,
                                     reward_bad=-1.0, reward_any=-0.1), 64, 700, 4, 35, True),
+    # six locations on a 5 x 3 pseudo-wall map: a location count that is no power of two (state / obs encodings
+    # L (L + 1), integers(6) with a Lemire threshold of 4)
+    "taxi_six_locs_3pass_hansen": (TX, dict(map=["R: :G", " : : ", "P: :W", " : : ", "Y: :B"], hansen_obs=True,
+                                            num_passengers=3, time_limit=60), 64, 400, 5, 36, True),
     # ---- C-ROOMS (crooms.py), float64 ----
     "crooms_yx_vmdp": (CR, dict(obs_type="vector_mdp"), 64, 400, 0, 41, True),
     "crooms_vel_vgmdp_randgoal": (CR, dict(obs_type="vector_goal_mdp", use_velocity=True, goal_xy=None,

@@ -11,6 +11,7 @@ import numpy as np
 from fixtures import grid_table_oracle
 from oracle.draws import NumpyDraws
 from oracle.gridworld import sample_effective_action
+from stream_plant import plant_word, state_with_output_word  # noqa: F401  (the edge tests import them from here)
 
 TWO53 = float(2 ** 53)
 
@@ -130,30 +131,6 @@ def threshold_rows(n, p):
     eff = sample_effective_action(action_probability_matrix(n, p)[act], k.astype(np.float64) * 2.0 ** -53)
     keep = eff < n
     return act[keep], k[keep], [(int(a), int(x)) for a, x in zip(act[~keep], k[~keep])]
-
-
-def _rotl64(x, r):
-    return ((x << r) | (x >> ((64 - r) & 63))) & ((1 << 64) - 1)
-
-
-def state_with_output_word(x, seed):
-    """A PCG64 state whose output (XSL-RR of the state itself, numpy steps first and then outputs) is the 64-bit
-    word x; the high half, which fixes the rotation, comes from `seed`."""
-    from oracle.pcg64 import pcg_output
-    hi = int(np.random.default_rng(seed).integers(0, 2 ** 63)) * 2 + 1
-    lo = hi ^ _rotl64(x, hi >> 58)
-    s = (hi << 64) | lo
-    assert pcg_output(s) == x
-    return s
-
-
-def plant_word(inc, pos, word, seed=0):
-    """The numpy PCG64 state dict from which draw `pos` (0-based) of the next Generator.random(B) comes from the
-    64-bit word `word`: the state with that output, stepped back pos + 1 draws."""
-    from oracle.pcg64 import MASK128, pcg_advance_params
-    a, c = pcg_advance_params((1 << 128) - (pos + 1), inc)
-    s0 = (a * state_with_output_word(word, seed) + c) & MASK128
-    return {"bit_generator": "PCG64", "state": {"state": s0, "inc": inc}, "has_uint32": 0, "uinteger": 0}
 
 
 def planted_words(n, p):

@@ -10,7 +10,7 @@ import pytest
 
 from fixtures import digest, load_case, load_index, step_actions
 from oracle import gridworld
-from oracle.pcg64 import MASK128, PCG64, lemire_threshold, pcg_advance_params, pcg_output
+from stream_plant import rejected_word, state_before, state_with_output_half
 
 pytestmark = pytest.mark.gpu
 
@@ -134,41 +134,13 @@ def test_rooms_random_goal_two_pass_large(gpu_device):
 
 
 # ---------------------------------------------------------------- forced Lemire rejections ----
-def _rotl(x, r):
-    return ((x << r) | (x >> ((64 - r) & 63))) & ((1 << 64) - 1)
-
-
-def _state_with_output_half(half_value, half, hi_seed):
-    """A PCG64 state whose output has the given low (half=0) or high (half=1) 32 bits."""
-    rng = np.random.default_rng(hi_seed)
-    hi = int(rng.integers(0, 2 ** 63)) * 2 + 1
-    other = int(rng.integers(0, 2 ** 32))
-    x = (other << 32) | half_value if half == 0 else (half_value << 32) | other
-    rot = hi >> 58
-    lo = hi ^ _rotl(x, rot)
-    s = (hi << 64) | lo
-    assert pcg_output(s) == x
-    return s
-
-
-def _rejected_word(n, k=1):
-    thr = lemire_threshold(n)
-    for kk in range(k, k + 10000):
-        r = -(-(kk << 32) // n)
-        if r < (1 << 32) and (r * n) & 0xFFFFFFFF < thr:
-            return r
-    raise AssertionError
-
-
 def _plant(inc, B, words, n):
     """Start state s0 (has_uint32=0) such that each word position in `words` (counted after
     random(B)) is a rejected Lemire draw for range n."""
     # plant the first word by construction, the others by searching is impractical; use one
     w = words[0]
     q, half = w >> 1, w & 1
-    s_star = _state_with_output_half(_rejected_word(n), half, w)
-    a, c = pcg_advance_params((1 << 128) - (B + q + 1), inc)
-    return (a * s_star + c) & MASK128
+    return state_before(state_with_output_half(rejected_word(n), half, w), inc, B + q)
 
 
 @pytest.mark.parametrize("word", [0, 1, 777, 4094])

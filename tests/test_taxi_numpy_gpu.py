@@ -15,7 +15,8 @@ from fixtures import digest, load_case, step_actions
 
 pytestmark = pytest.mark.gpu
 
-FIXTURES = ["taxi_hansen_b64", "taxi_plain_b256", "taxi_ext_hansen", "taxi_2pass_hansen", "taxi_ext_3pass_rew"]
+FIXTURES = ["taxi_hansen_b64", "taxi_plain_b256", "taxi_ext_hansen", "taxi_2pass_hansen", "taxi_ext_3pass_rew",
+            "taxi_six_locs_3pass_hansen"]
 
 
 def _kw(kw):

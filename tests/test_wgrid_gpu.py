@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from oracle import gridworld
-from oracle.pcg64 import MASK128, lemire_threshold, pcg_advance_params, pcg_output
+from stream_plant import np_state, rejected_word, state_before, state_with_output_half
 
 pytestmark = pytest.mark.gpu
 
@@ -137,30 +137,6 @@ def test_wgrid_halo_and_forced_window_misses(knobs, gpu_device):
     _check_chunks(env, ora, (12, 5), action_seed=9, n_act=4)
 
 
-def _rejected_word(n, k=1):
-    thr = lemire_threshold(n)
-    for kk in range(k, k + 10000):
-        r = -(-(kk << 32) // n)
-        if r < (1 << 32) and (r * n) & 0xFFFFFFFF < thr:
-            return r
-    raise AssertionError
-
-
-def _rotl(x, r):
-    return ((x << r) | (x >> ((64 - r) & 63))) & ((1 << 64) - 1)
-
-
-def _state_with_output_half(half_value, half, seed):
-    rng = np.random.default_rng(seed)
-    hi = int(rng.integers(0, 2 ** 63)) * 2 + 1
-    other = int(rng.integers(0, 2 ** 32))
-    x = (other << 32) | half_value if half == 0 else (half_value << 32) | other
-    lo = hi ^ _rotl(x, hi >> 58)
-    s = (hi << 64) | lo
-    assert pcg_output(s) == x
-    return s
-
-
 @pytest.mark.parametrize("word", [3, 2001, 40000])
 def test_wgrid_planted_rejection_inside_launch(word, gpu_device):
     """The PCG64 state is set so that half-word `word` of the next step's choice() stream is a rejected Lemire
@@ -178,10 +154,8 @@ def test_wgrid_planted_rejection_inside_launch(word, gpu_device):
             return
         inc = ora.gen.bit_generator.state["state"]["inc"]
         q, half = word >> 1, word & 1
-        s_star = _state_with_output_half(_rejected_word(n), half, word)
-        a, c = pcg_advance_params((1 << 128) - (B + q + 1), inc)
-        st = {"bit_generator": "PCG64", "state": {"state": (a * s_star + c) & MASK128, "inc": inc},
-              "has_uint32": 0, "uinteger": 0}
+        s_star = state_with_output_half(rejected_word(n), half, word)
+        st = np_state(state_before(s_star, inc, B + q), inc)
         env.rng_state = st
         ora.gen.bit_generator.state = st
 
