@@ -237,6 +237,7 @@ int gp_debug_set(const char* key, int64_t value) {
   else if (!strcmp(key, "xg_spb_min")) g_dbg.xg_spb_min = (int)value;
   else if (!strcmp(key, "persist_bpc")) g_dbg.persist_bpc = (int)value;
   else if (!strcmp(key, "ctrl_lds_max")) g_dbg.ctrl_lds_max = (int)value;
+  else if (!strcmp(key, "pomdp_lds_max")) g_dbg.pomdp_lds_max = (int)value;
   else if (!strcmp(key, "stats_lds_max")) g_dbg.stats_lds_max = (int)value;
   else if (!strcmp(key, "xg_graph")) gp_xg_graph_knob = (int)value;  // (crooms.hip: read at create)
   else {
@@ -310,6 +311,9 @@ int gp_create(int kind, const void* config, int64_t num_envs, int device, int rn
       break;
     case GP_KIND_HEAVENHELL:
       be = make_heavenhell_backend((const gp_heavenhell_config*)config, num_envs, device, rng_mode, &err);
+      break;
+    case GP_KIND_POMDP:
+      be = make_pomdp_backend((const gp_pomdp_config*)config, num_envs, device, rng_mode, &err);
       break;
     default: gp_set_error("gp_create: unknown kind %d", kind); return GP_E_INVALID;
   }

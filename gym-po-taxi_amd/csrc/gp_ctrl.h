@@ -1,6 +1,6 @@
 // gp_ctrl.h — the tabular finite-state controller of the closed-loop rollouts (gp_set_controller; semantics in
 // include/gym_po_amd.h), one copy for the kinds that run it (grid.hip with its populations, rocksample.hip, anttag.hip,
-// taxi.hip, heavenhell.hip, crooms.hip). Per env-step one Philox block tagged CTRL_TAG picks j = action * M + next_node
+// taxi.hip, heavenhell.hip, crooms.hip, pomdp.hip, which also runs ctrl_search on its model's own rows). Per env-step one Philox block tagged CTRL_TAG picks j = action * M + next_node
 // from the threshold row of (node, obs). Device side: the view of an installed table (CtrlDev), the node clamp
 // (ctrl_clamp_node), the pick (ctrl_pick over ctrl_search) and the split of j (ctrl_action, ctrl_node). Host side: the
 // validation of a table (ctrl_validate_rows) and the owner of an installed one (CtrlHost: install / clear, the LDS
@@ -14,11 +14,11 @@
 #include "gp_internal.h"
 
 // the env draws carry 0x67706f21 (grid) / 0x726f636b (rocksample) / 0x616e7431 (anttag) / 0x74617869 (taxi) /
-// 0x6868656c (heavenhell) / 0x63726f6f and 0x6d733121 (crooms)
+// 0x6868656c (heavenhell) / 0x63726f6f and 0x6d733121 (crooms) / 0x706f6d64 (pomdp)
 constexpr uint32_t CTRL_TAG = 0x67706f63u;
 // Largest dynamic LDS per block (env tables + controller table) up to which the kinds that stage the table in LDS
-// (grid.hip, taxi.hip, heavenhell.hip, crooms.hip) do so by default; the knob ctrl_lds_max overrides it, up to 60 KB
-// (CtrlHost::stage).
+// (grid.hip, taxi.hip, heavenhell.hip, crooms.hip, pomdp.hip) do so by default; the knob ctrl_lds_max overrides it, up
+// to 60 KB (CtrlHost::stage). pomdp.hip's budget for its model blob (knob pomdp_lds_max) has the same default and cap.
 constexpr int CTRL_LDS_BUDGET = 32 * 1024;
 constexpr int CTRL_MAX_L = 64;  // A * M: j / M by the 16-bit magic multiply is exact for j < 64
 struct CtrlDev {

@@ -44,7 +44,8 @@ struct GpDebugKnobs {
   int wg_fill_simd = 0;     // GRID windowed kernel: per-SIMD window-row deltas, 4 signed nibbles (0 = WG_FILL_SIMD)
   int64_t wg_fill_wave = 0; // GRID windowed kernel: per-wave deltas on top, 8 signed nibbles (wave 0 lowest)
   int ctrl_lds_max = -1;    // GRID / TAXI / HEAVENHELL / CROOMS closed-loop rollouts: dynamic LDS bytes per block up to which the controller table is staged in LDS (0 = never; -1 = gp_ctrl.h CTRL_LDS_BUDGET; at most 60 KB); read by gp_set_controller
-  int stats_lds_max = -1;   // gp_controller_stats: LDS bytes per block up to which one controller's tables are accumulated in a block-private LDS histogram (0 = never: global atomics; -1 = ctrl_stats.hip STATS_LDS_BUDGET; at most 60 KB); read at every call
+  int pomdp_lds_max = -1;   // POMDP: bytes up to which the model blob (the T / O / R tables) is staged in dynamic LDS (0 = never: global memory; -1 = gp_ctrl.h CTRL_LDS_BUDGET; at most 60 KB); read at gp_create
+  int stats_lds_max = -1;  // gp_controller_stats: LDS bytes per block up to which one controller's tables are accumulated in a block-private LDS histogram (0 = never: global atomics; -1 = ctrl_stats.hip STATS_LDS_BUDGET; at most 60 KB); read at every call
   int persist_bpc = 0;      // TAXI / CROOMS / ANT-TAG / ROCKSAMPLE / HEAVENHELL streaming rollouts: blocks per CU (0 = every resident block, persistent_grid); TAXI keeps the value of gp_create for its closed-loop grid (set_controller)
 };
 const GpDebugKnobs& gp_debug_knobs();
@@ -113,8 +114,8 @@ struct EnvBackend {
   }
   // Closed-loop rollouts (gp_set_controller / gp_rollout_controller / gp_controller_nodes): GRID in philox mode,
   // ROCKSAMPLE, ANTTAG with the index obs in philox mode, TAXI with the Hansen obs in philox mode, HEAVENHELL,
-  // CROOMS with a scalar obs and discrete actions in philox mode.
-  // What the six share lives in gp_ctrl.h (CtrlHost: install / clear, the LDS staging rule, the node plane, the
+  // CROOMS with a scalar obs and discrete actions in philox mode, POMDP.
+  // What the seven share lives in gp_ctrl.h (CtrlHost: install / clear, the LDS staging rule, the node plane, the
   // rollout_controller precondition; the device helpers of the pick); a kind keeps its refusals, its kernels and
   // the sizing of its closed-loop grid.
   virtual int set_controller(int n_nodes, int n_obs, const uint32_t* thr_host) {
@@ -141,7 +142,7 @@ struct EnvBackend {
     gp_set_error("controller populations are not supported by this env kind (GRID only)");
     return GP_E_UNSUPPORTED;
   }
-  // Controller statistics (gp_controller_stats): the six kinds with closed-loop rollouts answer the shape of what is
+  // Controller statistics (gp_controller_stats): the seven kinds with closed-loop rollouts answer the shape of what is
   // installed (GP_E_STATE: nothing is); the call itself is kind-independent (ctrl_stats.hip).
   virtual int controller_shape(CtrlShape* out) const {
     gp_set_error("controllers are not supported by this env kind");
@@ -216,6 +217,8 @@ std::unique_ptr<EnvBackend> make_rocksample_backend(const gp_rocksample_config* 
                                                     int rng_mode, int* err);
 std::unique_ptr<EnvBackend> make_heavenhell_backend(const gp_heavenhell_config* cfg, int64_t B, int device,
                                                     int rng_mode, int* err);
+std::unique_ptr<EnvBackend> make_pomdp_backend(const gp_pomdp_config* cfg, int64_t B, int device, int rng_mode,
+                                               int* err);
 
 // Small device-buffer owner.
 struct DevBuf {

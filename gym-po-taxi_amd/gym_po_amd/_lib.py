@@ -13,6 +13,7 @@ GP_OK = 0
 GP_E_DEVICE = -5
 GP_KIND_GRID, GP_KIND_TAXI, GP_KIND_CROOMS, GP_KIND_ANTTAG, GP_KIND_CARFLAG, GP_KIND_ROCKSAMPLE = 1, 2, 3, 4, 5, 6
 GP_KIND_HEAVENHELL = 7
+GP_KIND_POMDP = 8
 GP_RNG_NUMPY, GP_RNG_PHILOX, GP_RNG_REPLAY = 0, 1, 2
 RNG_MODES = {"numpy": GP_RNG_NUMPY, "philox": GP_RNG_PHILOX, "replay": GP_RNG_REPLAY}
 GP_DTYPE_I32, GP_DTYPE_U8, GP_DTYPE_F32, GP_DTYPE_F64 = 0, 1, 2, 3
@@ -80,6 +81,14 @@ class HeavenHellConfig(ctypes.Structure):
                 ("obs_base", _i32p), ("obs_base_n", ctypes.c_int32), ("keep_thr", ctypes.c_uint32),
                 ("time_limit", ctypes.c_int32), ("heaven_reward", ctypes.c_float), ("hell_reward", ctypes.c_float),
                 ("step_reward", ctypes.c_float), ("wall_reward", ctypes.c_float)]
+
+
+class PomdpConfig(ctypes.Structure):
+    _fields_ = [("n_states", ctypes.c_int32), ("n_actions", ctypes.c_int32), ("n_obs", ctypes.c_int32),
+                ("time_limit", ctypes.c_int32), ("trans_thr", ctypes.POINTER(ctypes.c_uint32)),
+                ("obs_thr", ctypes.POINTER(ctypes.c_uint32)), ("start_thr", ctypes.POINTER(ctypes.c_uint32)),
+                ("reset_obs_thr", ctypes.POINTER(ctypes.c_uint32)), ("reward", ctypes.POINTER(ctypes.c_float)),
+                ("terminal", ctypes.POINTER(ctypes.c_uint8))]
 
 
 # every symbol include/gym_po_amd.h declares: name -> (restype, argtypes)

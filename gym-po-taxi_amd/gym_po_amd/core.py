@@ -291,7 +291,8 @@ class NativeVecEnv:
         """Install the tabular controller of the closed-loop rollouts (FourRooms / ROOMS with a scalar obs in
         rng_mode='philox', RockSample, where A * M may not exceed 64, AntTagGridEnv with obs_type='index' in
         rng_mode='philox', TaxiVecEnv with hansen_obs=True in rng_mode='philox', scalar or one-hot: the table is
-        indexed by the scalar Hansen obs either way, HeavenHellGridEnv with either obs_type, and CRoomsEnv with
+        indexed by the scalar Hansen obs either way, HeavenHellGridEnv with either obs_type, TabularPOMDPEnv (any
+        model; A * M may not exceed 64; the obs conditioning a step is the env's stored last obs), and CRoomsEnv with
         action_type 'cardinal' (A = 4) or 'ordinal' (A = 8) and a scalar obs_type (hansen, hansen8, mdp, mdp_goal,
         room, room_goal) in rng_mode='philox'; its 'yx' actions, vector / grid obs and numpy / replay modes raise
         GymPoError naming the condition), or remove it when both arguments are None. `probs`: float [M, n_obs, A, M], the joint probability of (action, next node) given

@@ -63,6 +63,7 @@ extern "C" {
 #define GP_KIND_CARFLAG 5 /* Car-Flag: 1-D heaven/hell POMDP (car_flag.py) */
 #define GP_KIND_ROCKSAMPLE 6 /* RockSample (Smith & Simmons 2004), build-defined rules: gp_rocksample_config */
 #define GP_KIND_HEAVENHELL 7 /* grid Heaven-Hell (the task of ant_heaven_hell.py), build-defined rules: gp_heavenhell_config */
+#define GP_KIND_POMDP 8 /* tabular POMDP (T / O / R tables), build-defined rules: gp_pomdp_config */
 
 /* ---- RNG modes ---- */
 #define GP_RNG_NUMPY 0   /* seed-identical to numpy Generator(PCG64(SeedSequence(seed))): GRID, CROOMS, TAXI, CARFLAG */
@@ -240,6 +241,41 @@ typedef struct gp_heavenhell_config {
   float heaven_reward, hell_reward, step_reward, wall_reward;
 } gp_heavenhell_config;
 
+/* Tabular POMDP (GP_KIND_POMDP; GP_RNG_PHILOX only: there is no reference stream, so GP_RNG_NUMPY / GP_RNG_REPLAY
+ * return GP_E_UNSUPPORTED). A finite POMDP given as its tables (Cassandra's T / O / R); build-defined, no reference
+ * counterpart. Everything that decides an outcome arrives as integers: no float arithmetic and no libm call of the
+ * library decides a result (as with RockSample's sensor_thr).
+ *   sizes    n_states S, n_actions A, n_obs O: 1 <= S <= 65,536, 1 <= A <= 64, 1 <= O <= 65,536. The library pads each
+ *            stored row to 16-B quads with 2^31 (Sp = (S + 3) & ~3, Op = (O + 3) & ~3); S A Sp <= 2^28 and
+ *            A S Op <= 2^28.
+ *   tables   every threshold row holds cumulative probabilities scaled to 2^31, nondecreasing within [0, 2^31] and
+ *            ending at 2^31 (gp_set_controller's rule).
+ *   state    per env the state s, elapsed, and the last observation (a draw, not a function of the state: the handle
+ *            keeps it); gp_get_state / gp_set_state exchange (state, elapsed, obs) as int32 [B] each (set clamps to
+ *            [0, S), [0, 65535] and [0, O); NULL leaves a field alone).
+ *   actions  [-A, 0) wraps as numpy indexing does; anything else is flagged (GP_E_DEVICE from gp_check) and clamped.
+ *   draws    one Philox4x32-10 block per (env, step), counter (env, step_lo, step_hi, 0x706f6d64) under the handle's
+ *            key; with y_i = x_i >> 1: s' = #{i < S : y0 >= trans_thr[s][a][i]}; if the episode goes on, obs =
+ *            #{i < O : y1 >= obs_thr[a][s'][i]}; if the step ended it, s0 = #{i < S : y2 >= start_thr[i]} and obs =
+ *            #{i < O : y3 >= reset_obs_thr[s0][i]}. gp_reset takes y2, y3 from the block of its own step index. Counts
+ *            are clamped to S - 1 / O - 1.
+ *   step     reward = reward[s][a][s'], terminated = terminal[s'], truncated = elapsed + 1 >= time_limit, independent
+ *            of terminated. An episode end resets the env in the same step, and the step's obs is the reset obs.
+ *   obs      int32 [B], the stored draw; n_obs = O.
+ * GP_E_INVALID, naming the fault: a size outside its range, a NULL table, a padded table above 2^28 entries, a threshold
+ * row that is not nondecreasing within [0, 2^31] or does not end at 2^31 (the table and the row are named), time_limit
+ * outside [1, 65535] (elapsed is kept in 16 bits). */
+typedef struct gp_pomdp_config {
+  int32_t n_states, n_actions, n_obs;
+  int32_t time_limit;
+  const uint32_t* trans_thr;     /* [S][A][S] row (s, a): cumulative P(s' | s, a) * 2^31                  */
+  const uint32_t* obs_thr;       /* [A][S][O] row (a, s'): cumulative P(o | a, s') * 2^31 (O: a : s' : o) */
+  const uint32_t* start_thr;     /* [S] the start-state law                                              */
+  const uint32_t* reset_obs_thr; /* [S][O] row s0: the law of the first obs given the start state        */
+  const float* reward;           /* [S][A][S] indexed (s, a, s')                                         */
+  const uint8_t* terminal;       /* [S] nonzero: entering the state ends the episode                     */
+} gp_pomdp_config;
+
 typedef struct gp_env gp_env;
 
 const char* gp_last_error(void);
@@ -288,7 +324,7 @@ void gp_plan_destroy(gp_plan* plan);
 /* ---- closed-loop rollouts: a tabular finite-state controller evaluated inside the rollout kernel ----
  * GRID in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN / GP_OBS_TABLE), ROCKSAMPLE (either obs), ANTTAG with the
  * index obs (obs_index = 1) in GP_RNG_PHILOX, TAXI with the Hansen obs (GP_OBS_HANSEN, one_hot 0 or 1) in
- * GP_RNG_PHILOX, HEAVENHELL (any obs base), and CROOMS in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN /
+ * GP_RNG_PHILOX, HEAVENHELL (any obs base), POMDP, and CROOMS in GP_RNG_PHILOX with a scalar obs (GP_OBS_HANSEN /
  * GP_OBS_TABLE) and discrete actions (action_kind 4 or 8); every other kind, rng mode and obs kind:
  * GP_E_UNSUPPORTED. (No reference counterpart: the reference's agents act from the host, one step() per action.)
  *
@@ -338,6 +374,11 @@ void gp_plan_destroy(gp_plan* plan);
  * "4": Hansen-4 with 4 actions and M = 1 is 1.25 KB; Hansen-8 with 8 actions is 72 KB at M = 1 and mdp_goal has
  * 40,000 obs values: global memory). An obs the env computes outside [0, n_obs) (cell_size > 1 puts positions on
  * wall cells, whose table value is -1, as in the reference) is clamped and flagged like any other.
+ * POMDP: the obs is the stored last obs of the env (the reset's draw, then each step's); the env draws carry 0x706f6d64.
+ * A is the model's (1..64), so L = A M <= 64; rows hold exactly L entries and are padded to 16-B quads as ROCKSAMPLE's
+ * are where L is no multiple of 4. n_obs is the caller's (the obs space has O values). The table is staged in LDS behind
+ * the env's LDS bytes (the model blob when it is in LDS itself, see "pomdp_lds_max" below, else nothing) when both fit
+ * the "ctrl_lds_max" budget, else read from global memory: four combinations, one kernel instance each.
  *
  * gp_set_controller validates the table, uploads it synchronously and zeroes every node; thr_host = NULL removes the
  * controller. The nodes (uint8 [B], handle state) persist across calls; gp_reset zeroes them; gp_step / gp_rollout
@@ -400,7 +441,7 @@ int gp_controller_scores(gp_env* env, double* out, int cap_rows, int clear);
 /* ---- controller statistics: visit counts and return-to-go sums per table cell, exact integers ----
  * The sufficient statistics of policy-gradient, Monte Carlo policy-iteration and EM steps over a controller's
  * parameters, from K stored closed-loop steps, in one launch. Every kind with closed-loop rollouts (GRID, ROCKSAMPLE,
- * ANTTAG, TAXI, HEAVENHELL, CROOMS); the others: GP_E_UNSUPPORTED. (No reference counterpart.)
+ * ANTTAG, TAXI, HEAVENHELL, CROOMS, POMDP); the others: GP_E_UNSUPPORTED. (No reference counterpart.)
  *
  * The call is a pure function of the planes it is given: it reads nothing of the env's state and needs no gp_reset.
  * The handle supplies the shape: M = n_nodes and n_obs of the installed controller, A = the env's action count, and
@@ -448,7 +489,8 @@ int gp_controller_stats(gp_env* env, int K, const int32_t* obs0, const int32_t* 
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
- * mask, elapsed. HEAVENHELL: agent cell, heaven side (0 left, 1 right), elapsed. CARFLAG: s f32[B,3]
+ * mask, elapsed. HEAVENHELL: agent cell, heaven side (0 left, 1 right), elapsed. POMDP: state, elapsed, last obs.
+ * CARFLAG: s f32[B,3]
  * (position, velocity, direction), elapsed i32[B], heavens f32[B] (+-1), priests f32[B] (+-0.5; set takes
  * both by sign).
  * TAXI packs n_dropoffs into 4 bits: gp_set_state clamps it to [0, 15] and a goal move from 15 leaves it at 15
@@ -496,8 +538,9 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * "fused_tile_envs", "philox_step" (GP_RNG_PHILOX: the counter's step index that the next reset / step draws
  * with; a K-step rollout, open or closed loop, advances it by K), "controller_nodes" (node count of the installed
  * controller, 0 = none), "controller_lds" (1 = its table is staged in LDS; ROCKSAMPLE, ANTTAG: always 0); ROCKSAMPLE,
- * ANTTAG, TAXI, HEAVENHELL and CROOMS answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
- * rollout, 0 = no controller). GRID also: "controller_population" (P of the installed population, 0 = none),
+ * ANTTAG, TAXI, HEAVENHELL, CROOMS and POMDP answer the last three too, TAXI also "controller_blocks" (persistent grid size of its closed-loop
+ * rollout, 0 = no controller). POMDP also: "pomdp_lds" (1 = the model blob is staged in LDS, 0 = read from global
+ * memory) and "pomdp_model_bytes" (the blob's size, what "pomdp_lds_max" is compared with). GRID also: "controller_population" (P of the installed population, 0 = none),
  * "controller_group_envs" (its G), "controller_group_multiple" (1024: what G must be a multiple of); with a population
  * "controller_nodes" and "controller_lds" answer for one controller's table. Every kind with closed-loop rollouts
  * also: "controller_n_obs" and "controller_actions" (n_obs of the installed table and the env's A: the shape
@@ -559,7 +602,8 @@ int gp_profile_read_resolver(gp_env* env, double* total_ms, int64_t* n_launches)
  *   resident block; TAXI keeps the value it was created with for its closed-loop grid too), "stats_lds_max"
  *   (gp_controller_stats, read at every call instead: one controller's tables are accumulated in a block-private LDS
  *   histogram when they take at most this many bytes, 12 per cell, at most 60 KB; 0 = always global atomics, -1 = the
- *   default, 40 KiB).
+ *   default, 40 KiB), "pomdp_lds_max" (POMDP, read at gp_create: the model blob is staged in dynamic LDS when it takes
+ *   at most this many bytes, at most 60 KB; 0 = always global memory, -1 = the default, 32 KB).
  *   gp_debug_reset restores the defaults. Unknown key: GP_E_INVALID. */
 int gp_debug_set(const char* key, int64_t value);
 void gp_debug_reset(void);
