@@ -45,6 +45,9 @@ const char* gp_derr_text(uint32_t flags) {
   if (flags & GP_DERR_STATS)
     strncat(buf, "gp_controller_stats met a visit outside the table or a return-to-go of 2^31 or more, NaN included (the "
                  "visit was skipped; the tables lack it); ", sizeof(buf) - strlen(buf) - 1);
+  if (flags & GP_DERR_BELIEF)
+    strncat(buf, "a belief filter step met an obs of probability zero under the stored belief (the belief was replaced "
+                 "by the prior); ", sizeof(buf) - strlen(buf) - 1);
   return buf;
 }
 
@@ -239,6 +242,7 @@ int gp_debug_set(const char* key, int64_t value) {
   else if (!strcmp(key, "ctrl_lds_max")) g_dbg.ctrl_lds_max = (int)value;
   else if (!strcmp(key, "pomdp_lds_max")) g_dbg.pomdp_lds_max = (int)value;
   else if (!strcmp(key, "stats_lds_max")) g_dbg.stats_lds_max = (int)value;
+  else if (!strcmp(key, "belief_onchip_max")) g_dbg.belief_onchip_max = (int)value;
   else if (!strcmp(key, "xg_graph")) gp_xg_graph_knob = (int)value;  // (crooms.hip: read at create)
   else {
     gp_set_error("gp_debug_set: unknown key '%s'", key);
@@ -504,6 +508,59 @@ int gp_controller_stats(gp_env* env, int K, const int32_t* obs0, const int32_t* 
   if (K == 0) return GP_OK;
   return ctrl_stats_launch(c, env->be->B, K, obs0, obs, actions, nodes, next_nodes, rew, term, trunc, bootstrap, gamma,
                            counts, ret_q, &env->be->stats_path, (hipStream_t)stream);
+}
+
+int gp_belief_enable(gp_env* env, const float* prior) {
+  GP_REQUIRE_ENV();
+  return env->be->belief_enable(prior);
+}
+
+int gp_belief_disable(gp_env* env) {
+  GP_REQUIRE_ENV();
+  return env->be->belief_disable();
+}
+
+int gp_belief_get(gp_env* env, float* out, void* stream) {
+  GP_REQUIRE_ENV();
+  if (!out) {
+    gp_set_error("gp_belief_get: null buffer");
+    return GP_E_INVALID;
+  }
+  return env->be->belief_get(out, (hipStream_t)stream);
+}
+
+int gp_belief_set(gp_env* env, const float* in, void* stream) {
+  GP_REQUIRE_ENV();
+  if (!in) {
+    gp_set_error("gp_belief_set: null buffer");
+    return GP_E_INVALID;
+  }
+  return env->be->belief_set(in, (hipStream_t)stream);
+}
+
+int gp_belief_filter(gp_env* env, int K, const int32_t* actions, const int32_t* obs, const uint8_t* term,
+                     const uint8_t* trunc, void* stream) {
+  GP_REQUIRE_ENV();
+  if (K < 0 || (K > 0 && (!actions || !obs || !term || !trunc))) {
+    gp_set_error("gp_belief_filter: bad arguments (K >= 0; no plane may be null)");
+    return GP_E_INVALID;
+  }
+  return env->be->belief_filter(K, actions, obs, term, trunc, (hipStream_t)stream);
+}
+
+int gp_set_belief_policy(gp_env* env, int n_vectors, const float* alpha, const int32_t* vec_action) {
+  GP_REQUIRE_ENV();
+  return env->be->set_belief_policy(n_vectors, alpha, vec_action);
+}
+
+int gp_rollout_belief(gp_env* env, int K, void* obs, int32_t* actions, int32_t* vec, float* value, float* rew,
+                      uint8_t* term, uint8_t* trunc, void* stream) {
+  GP_REQUIRE_ENV();
+  if (K < 0) {
+    gp_set_error("gp_rollout_belief: bad arguments");
+    return GP_E_INVALID;
+  }
+  return env->be->rollout_belief(K, obs, actions, vec, value, rew, term, trunc, (hipStream_t)stream);
 }
 
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream) {

@@ -251,6 +251,8 @@ __device__ __forceinline__ void store4(T* __restrict__ p, int env0, int B, const
                             // node count (set through gp_controller_nodes): the device clamped it
 #define GP_DERR_STATS 64u   // gp_controller_stats: a visit whose node, obs, action or next node lies outside the table,
                             // or whose return-to-go is not below 2^31 in magnitude (NaN included): the visit was skipped
+#define GP_DERR_BELIEF 128u // POMDP belief filter: a step whose normaliser was not a positive finite number (the obs has
+                            // probability zero under the stored belief): the belief was replaced by the prior
 // numpy indexing of an n-row table accepts a in [-n, n) (negatives wrap); anything else raises.
 __device__ __forceinline__ bool action_out_of_range(int a, int n) { return (uint32_t)(a + n) >= (uint32_t)(2 * n); }
 __device__ __forceinline__ void flag_bad_action(uint32_t* derr) { atomicOr(derr, GP_DERR_ACTION); }

@@ -46,6 +46,7 @@ struct GpDebugKnobs {
   int ctrl_lds_max = -1;    // GRID / TAXI / HEAVENHELL / CROOMS closed-loop rollouts: dynamic LDS bytes per block up to which the controller table is staged in LDS (0 = never; -1 = gp_ctrl.h CTRL_LDS_BUDGET; at most 60 KB); read by gp_set_controller
   int pomdp_lds_max = -1;   // POMDP: bytes up to which the model blob (the T / O / R tables) is staged in dynamic LDS (0 = never: global memory; -1 = gp_ctrl.h CTRL_LDS_BUDGET; at most 60 KB); read at gp_create
   int stats_lds_max = -1;  // gp_controller_stats: LDS bytes per block up to which one controller's tables are accumulated in a block-private LDS histogram (0 = never: global atomics; -1 = ctrl_stats.hip STATS_LDS_BUDGET; at most 60 KB); read at every call
+  int belief_onchip_max = -1;  // POMDP belief filter: LDS bytes per block (8,192 per state: two buffers of 1,024 envs) up to which the beliefs of a block's envs stay in LDS across a launch (0 = never: global planes; -1 = whatever fits 60 KB beside the model blob); read by gp_belief_enable
   int persist_bpc = 0;      // TAXI / CROOMS / ANT-TAG / ROCKSAMPLE / HEAVENHELL streaming rollouts: blocks per CU (0 = every resident block, persistent_grid); TAXI keeps the value of gp_create for its closed-loop grid (set_controller)
 };
 const GpDebugKnobs& gp_debug_knobs();
@@ -155,6 +156,24 @@ struct EnvBackend {
     }
     *out = CtrlShape{M, n_obs, A, P > 0 ? P : 1, P > 0 ? G : 0, derr};
     return GP_OK;
+  }
+  // Belief filter and alpha-vector policies (gp_belief_* / gp_set_belief_policy / gp_rollout_belief): POMDP only.
+  int no_belief() const {
+    gp_set_error("belief filters are not supported by this env kind (POMDP only)");
+    return GP_E_UNSUPPORTED;
+  }
+  virtual int belief_enable(const float* prior) { return no_belief(); }
+  virtual int belief_disable() { return no_belief(); }
+  virtual int belief_get(float* out, hipStream_t s) { return no_belief(); }
+  virtual int belief_set(const float* in, hipStream_t s) { return no_belief(); }
+  virtual int belief_filter(int K, const int32_t* act, const int32_t* obs, const uint8_t* term, const uint8_t* trunc,
+                            hipStream_t s) {
+    return no_belief();
+  }
+  virtual int set_belief_policy(int n_vec, const float* alpha, const int32_t* vec_action) { return no_belief(); }
+  virtual int rollout_belief(int K, void* obs, int32_t* act, int32_t* vec, float* value, float* rew, uint8_t* term,
+                             uint8_t* trunc, hipStream_t s) {
+    return no_belief();
   }
   int stats_path = -1;  // the last gp_controller_stats launch: 1 = LDS histogram, 0 = global atomics (gp_query "stats_lds")
   virtual int valid_cells(int which, int32_t* out, int cap) const { return 0; }

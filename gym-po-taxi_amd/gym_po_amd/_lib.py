@@ -119,6 +119,13 @@ SIGNATURES = {
     "gp_controller_scores": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int]),
     "gp_controller_stats": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            ctypes.c_float, _vp, _vp, _vp]),
+    "gp_belief_enable": (ctypes.c_int, [_vp, _vp]),
+    "gp_belief_disable": (ctypes.c_int, [_vp]),
+    "gp_belief_get": (ctypes.c_int, [_vp, _vp, _vp]),
+    "gp_belief_set": (ctypes.c_int, [_vp, _vp, _vp]),
+    "gp_belief_filter": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "gp_set_belief_policy": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    "gp_rollout_belief": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_get_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_replay": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -172,6 +172,160 @@ class TabularPOMDPEnv(NativeVecEnv):
         self._set_state_raw([conv(state), conv(elapsed), conv(obs)])
         torch.cuda.current_stream(self.device).synchronize()
 
+    # ------------------------------------------------------------------ belief filter ----
+    # An exact Bayes filter kept per env on the device and a piecewise-linear (alpha-vector) policy over it
+    # (csrc/pomdp.hip; the rules are stated in include/gym_po_amd.h). reset() sets every belief from
+    # the prior and the reset obs; step(), rollout(), rollout_controller() and set_state() leave the beliefs alone, as
+    # they leave controller nodes alone: belief_filter() advances them over the planes those calls wrote.
+    _BELIEF_OUTPUTS = ("obs", "actions", "vec", "value", "rew", "term", "trunc")
+
+    def enable_belief(self, prior=None):
+        """Start tracking a belief [S] per env. `prior` [S]: the law of an episode's start state as the agent knows it
+        (validated: finite, >= 0, a positive sum; then normalised in float32 by the filter's sequential sum); None: the
+        env's start law as the filter's float32 law. Every belief is set from the prior and the env's stored obs, as
+        reset() does from then on. S <= 4,096. Calling it again replaces the prior."""
+        from ..belief import normalise_belief
+        fn = self._ctrl_fn("gp_belief_enable")
+        if prior is None:
+            _lib.check(fn(self._handle, None), "gp_belief_enable")
+            return
+        p = np.asarray(prior)
+        if p.shape != (self.n_states,):
+            raise ValueError(f"prior must be [S] = [{self.n_states}], got shape {p.shape}")
+        p = np.ascontiguousarray(_named("prior", normalise_belief, p))
+        _lib.check(fn(self._handle, ctypes.c_void_p(p.ctypes.data)), "gp_belief_enable")
+
+    def disable_belief(self):
+        """Stop tracking beliefs and free them (an installed policy stays)."""
+        _lib.check(self._ctrl_fn("gp_belief_disable")(self._handle), "gp_belief_disable")
+
+    @property
+    def belief(self):
+        """The belief of every env, float32 [B, S] on the device (a copy)."""
+        torch = _torch()
+        t = torch.empty((self.num_envs, self.n_states), dtype=torch.float32, device=self.device)
+        _lib.check(self._ctrl_fn("gp_belief_get")(self._handle, ctypes.c_void_p(t.data_ptr()), self._stream()),
+                   "gp_belief_get")
+        return t
+
+    def set_belief(self, b):
+        """Replace the beliefs by `b` [B, S] (float32 values are stored as given). ValueError for entries that are
+        negative or not finite and for a row whose sum is not positive."""
+        torch = _torch()
+        t = b if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float32))
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(t.shape) != (self.num_envs, self.n_states):
+            raise ValueError(f"set_belief: need [B, S] = [{self.num_envs}, {self.n_states}], got {tuple(t.shape)}")
+        if not bool((torch.isfinite(t) & (t >= 0)).all()) or not bool((t.sum(-1) > 0).all()):
+            raise ValueError("set_belief: entries must be finite and >= 0, and every row needs a positive sum")
+        _lib.check(self._ctrl_fn("gp_belief_set")(self._handle, ctypes.c_void_p(t.data_ptr()), self._stream()),
+                   "gp_belief_set")
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def belief_filter(self, actions, obs=None, term=None, trunc=None):
+        """Advance the stored beliefs over K stored steps: `actions` int32 [K, B], `obs` int32 [K, B] (the obs after
+        each step), `term` / `trunc` bool or uint8 [K, B], whoever wrote them (rollout(), rollout_controller(), a
+        replay); or, as the only argument, the dict rollout_controller() / rollout_belief() returned. A pure function
+        of the planes and the stored beliefs: the env's state is not read. Actions wrap and clamp as in step(), obs
+        values outside [0, O) are clamped; both are flagged (check())."""
+        torch = _torch()
+        if isinstance(actions, dict):
+            d = actions
+            if obs is not None or term is not None or trunc is not None:
+                raise ValueError("belief_filter: a dict of planes is the only argument")
+            missing = [n for n in ("actions", "obs", "term", "trunc") if n not in d]
+            if missing:
+                raise ValueError(f"belief_filter: the dict lacks {missing}")
+            actions, obs, term, trunc = d["actions"], d["obs"], d["term"], d["trunc"]
+        elif obs is None or term is None or trunc is None:
+            raise ValueError("belief_filter: needs actions, obs, term and trunc")
+
+        def plane(name, x, dt):
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+            if dt is torch.uint8 and t.dtype == torch.bool:
+                t = t.view(torch.uint8) if t.is_contiguous() else t.to(torch.uint8)
+            t = t.to(device=self.device, dtype=dt).contiguous()
+            if t.dim() != 2 or t.shape[1] != self.num_envs:
+                raise ValueError(f"belief_filter: {name} must be [K, B] = [K, {self.num_envs}], got {tuple(t.shape)}")
+            return t
+        a, o = plane("actions", actions, torch.int32), plane("obs", obs, torch.int32)
+        tm, tr = plane("term", term, torch.uint8), plane("trunc", trunc, torch.uint8)
+        K = a.shape[0]
+        if not (o.shape[0] == tm.shape[0] == tr.shape[0] == K):
+            raise ValueError("belief_filter: the planes differ in K")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(self._ctrl_fn("gp_belief_filter")(self._handle, K, ptr(a), ptr(o), ptr(tm), ptr(tr), self._stream()),
+                   "gp_belief_filter")
+
+    def set_belief_policy(self, alpha=None, actions=None):
+        """Install a piecewise-linear policy over the belief: `alpha` [N, S] (finite, |alpha| <= 1e30; stored as
+        float32) and `actions` int [N] in [0, A), the action of each vector (None: arange(N), which needs N == A, the
+        layout of `belief.qmdp_vectors`). The action of a step is that of the first vector that attains
+        max_j sum_s b[s] alpha[j, s] on the belief before the step. N <= 4,096 and N * S <= 2^22. alpha=None removes
+        the policy."""
+        fn = self._ctrl_fn("gp_set_belief_policy")
+        if alpha is None:
+            _lib.check(fn(self._handle, 0, None, None), "gp_set_belief_policy")
+            return
+        al = np.ascontiguousarray(np.asarray(alpha, dtype=np.float32))
+        if al.ndim != 2 or al.shape[1] != self.n_states or al.shape[0] < 1:
+            raise ValueError(f"alpha must be [N, S] = [N, {self.n_states}], got shape {al.shape}")
+        N = al.shape[0]
+        if actions is None:
+            if N != self.n_actions:
+                raise ValueError(f"set_belief_policy: {N} vectors and {self.n_actions} actions: name each vector's action")
+            actions = np.arange(N)
+        va = np.asarray(actions)
+        if va.shape != (N,) or va.dtype.kind not in "iu":
+            raise ValueError(f"actions must be integers [N] = [{N}], got {va.dtype} {va.shape}")
+        va = np.ascontiguousarray(va.astype(np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        _lib.check(fn(self._handle, N, ctypes.c_void_p(al.ctypes.data), ctypes.c_void_p(va.ctypes.data)),
+                   "gp_set_belief_policy")
+
+    def rollout_belief(self, K, out=None, store=_BELIEF_OUTPUTS):
+        """K closed-loop steps in ONE launch: each env's action is chosen on the device by the installed alpha-vector
+        policy from the env's belief, the env steps, and the belief is updated from the action and the new obs.
+        Returns a dict of the outputs named in `store`: obs int32 [K, B], actions int32 [K, B], vec int32 [K, B] (the
+        index of the maximising vector), value float32 [K, B] (its value on the belief before the step), rew float32
+        [K, B], term / trunc bool [K, B]. `out`, `store`, dtypes and the bool views follow rollout_controller(). No
+        random draw is spent on the choice: rollout() of `actions` on a twin env of the same seed reproduces every
+        output, the state and the metrics bit for bit."""
+        torch = _torch()
+        fn = self._ctrl_fn("gp_rollout_belief")
+        K = int(K)
+        if K < 0:
+            raise ValueError("K must be >= 0")
+        store = tuple(store)
+        for name in store:
+            if name not in self._BELIEF_OUTPUTS:
+                raise ValueError(f"store: unknown output {name!r} (one of {self._BELIEF_OUTPUTS})")
+        lead = (K, self.num_envs)
+        want = {"obs": (lead, torch.int32), "actions": (lead, torch.int32), "vec": (lead, torch.int32),
+                "value": (lead, torch.float32), "rew": (lead, torch.float32), "term": (lead, torch.uint8),
+                "trunc": (lead, torch.uint8)}
+        if out is not None and not isinstance(out, dict):
+            raise ValueError("out must be a dict of tensors by output name")
+        bufs = {}
+        for name in store:
+            shape, dt = want[name]
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            elif not isinstance(t, torch.Tensor):
+                raise ValueError(f"out {name}: expected a torch tensor")
+            elif tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"out {name}: need a contiguous {dt} tensor of shape {shape} on {self.device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device} (contiguous={t.is_contiguous()})")
+            bufs[name] = t
+        ptr = lambda name: ctypes.c_void_p(bufs[name].data_ptr()) if name in bufs else None  # noqa: E731
+        _lib.check(fn(self._handle, K, ptr("obs"), ptr("actions"), ptr("vec"), ptr("value"), ptr("rew"), ptr("term"),
+                      ptr("trunc"), self._stream()), "gp_rollout_belief")
+        res = dict(bufs)
+        for name in ("term", "trunc"):
+            if name in res:
+                res[name] = res[name].view(torch.bool)
+        return res
+
 
 def heaven_hell_pomdp(env):
     """(T, Z, R, start, terminal, reset_obs) of a `HeavenHellGridEnv`: the same task as tables. S = 2 H W with state =

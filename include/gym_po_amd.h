@@ -486,6 +486,64 @@ int gp_controller_stats(gp_env* env, int K, const int32_t* obs0, const int32_t* 
                         const uint8_t* trunc, const float* bootstrap, float gamma, int64_t* counts, int64_t* ret_q,
                         void* stream);
 
+/* ---- belief filter and alpha-vector policies (POMDP only; every other kind: GP_E_UNSUPPORTED) ----
+ * An exact Bayes filter kept per env on the device, a piecewise-linear policy over it, and a closed-loop rollout that
+ * does env step, filter update and action choice in one launch. Build-defined (no reference counterpart); pinned bit
+ * for bit to the numpy restatement tests/belief_oracle.py.
+ *
+ * Float laws. Built from the handle's integer thresholds: for a threshold row thr,
+ *   p[i] = (float)(uint32)(thr[i] - thr[i-1]) * 2^-31, thr[-1] = 0 (one round-to-nearest conversion, an exact scale;
+ *   numpy: np.diff(thr.astype(np.int64), prepend=0).astype(np.float32) * np.float32(2**-31)).
+ * Tf[s][a][s'] from trans_thr, Zf[a][s'][o] from obs_thr, Rf[s][o] from reset_obs_thr, the default prior from start_thr.
+ * Arithmetic. float32, every product and every sum rounded separately (no FMA), denormals kept, sums sequential in
+ * ascending index from +0, division correctly rounded.
+ * Filter step. Belief b[S], action a (wrapped / clamped exactly as gp_step does), stored obs o after the step,
+ * ended = term | trunc.
+ *   not ended: acc(s') = sum_s fl(b[s] Tf[s][a][s']); u(s') = terminal[s'] ? +0 : fl(Zf[a][s'][o] acc(s')) (a step that
+ *              did not end tells the agent that s' is not terminal)
+ *   ended:     u(s) = fl(prior[s] Rf[s][o]) (the stored obs is the reset obs)
+ *   both:      n = sum_s u(s); b'(s) = fl(u(s) / n). If !(n > 0) or n is not finite: b' = prior, and the handle is
+ *              flagged (gp_check: GP_E_DEVICE until the next seed).
+ * gp_reset, and gp_belief_enable, set b by the ended rule from each env's stored obs. gp_step, gp_rollout,
+ * gp_rollout_controller and gp_set_state leave the beliefs alone (as they leave controller nodes alone): advance them
+ * with gp_belief_filter over the planes those calls wrote.
+ * The device skips entries with Tf == 0 and whole columns with Zf == 0 or a terminal s': all operands are >= 0 and the
+ * accumulators start at +0, so the bits are those of the dense loop (beliefs given through gp_belief_set must be
+ * finite and >= 0 for that).
+ * Policy. N vectors alpha[N][S] (finite, |alpha| <= 1e30) and vec_action[N] in [0, A): v_j = sum_s fl(b[s] alpha[j][s]);
+ * j* is the first j that attains the maximum (replaced only on a strict >); the action is vec_action[j*], chosen from
+ * the belief before the step, as a controller chooses from the obs before the step. No random draw is spent: feeding
+ * the emitted actions to gp_rollout on a twin handle reproduces obs, rew, term, trunc, state and metrics bit for bit.
+ * Limits. Belief: S <= 4,096. Policy: N <= 4,096 and N S <= 2^22. Beyond them GP_E_INVALID. A failed allocation
+ * installs nothing.
+ *
+ * gp_belief_enable: prior float [S] (host) is used as given; NULL = the start law. Allocates two planes of S B floats,
+ *   builds the float laws, sets every belief by the reset rule; synchronous. Calling it again replaces the prior.
+ * gp_belief_disable frees them (a policy stays installed).
+ * gp_belief_get / gp_belief_set: device float [B][S]; values are stored as given. GP_E_STATE without a filter.
+ * gp_belief_filter advances the stored beliefs over K stored steps of planes [K,B] (actions int32, obs int32, term /
+ *   trunc uint8; device), whoever wrote them: gp_rollout, gp_rollout_controller, or a replay. A pure function of its
+ *   inputs and the stored beliefs; the env state is not read. Actions are wrapped and clamped as gp_step does
+ *   (flagged like there), obs values outside [0, O) are clamped and flagged (gp_check: GP_E_DEVICE).
+ * gp_set_belief_policy: alpha float [N][S], vec_action int32 [N] (host); N = 0 removes the policy.
+ * gp_rollout_belief: K closed-loop steps in one launch. obs int32 [K,B], actions int32 [K,B], vec int32 [K,B] (j*),
+ *   value float [K,B] (v_j*), rew float [K,B], term / trunc uint8 [K,B]; every output may be NULL. Accumulates
+ *   gp_metrics as gp_rollout does. GP_E_STATE before gp_reset, without an enabled filter or without a policy. The
+ *   beliefs after the launch are bit-equal to gp_belief_filter run over the planes it wrote.
+ * Placement: when two LDS buffers of a block's 1,024 beliefs (8,192 S bytes, gp_query "belief_onchip_bytes") fit 60 KB
+ * beside the model blob, and the knob "belief_onchip_max", the beliefs stay in LDS across the K steps of a launch;
+ * else they are read and written in the global planes. Bit-equal. gp_query: "belief" (0 / 1), "belief_onchip",
+ * "belief_vectors" (N of the installed policy). */
+int gp_belief_enable(gp_env* env, const float* prior);
+int gp_belief_disable(gp_env* env);
+int gp_belief_get(gp_env* env, float* out, void* stream);
+int gp_belief_set(gp_env* env, const float* in, void* stream);
+int gp_belief_filter(gp_env* env, int K, const int32_t* actions, const int32_t* obs, const uint8_t* term,
+                     const uint8_t* trunc, void* stream);
+int gp_set_belief_policy(gp_env* env, int n_vectors, const float* alpha, const int32_t* vec_action);
+int gp_rollout_belief(gp_env* env, int K, void* obs, int32_t* actions, int32_t* vec, float* value, float* rew,
+                      uint8_t* term, uint8_t* trunc, void* stream);
+
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
@@ -603,7 +661,10 @@ int gp_profile_read_resolver(gp_env* env, double* total_ms, int64_t* n_launches)
  *   (gp_controller_stats, read at every call instead: one controller's tables are accumulated in a block-private LDS
  *   histogram when they take at most this many bytes, 12 per cell, at most 60 KB; 0 = always global atomics, -1 = the
  *   default, 40 KiB), "pomdp_lds_max" (POMDP, read at gp_create: the model blob is staged in dynamic LDS when it takes
- *   at most this many bytes, at most 60 KB; 0 = always global memory, -1 = the default, 32 KB).
+ *   at most this many bytes, at most 60 KB; 0 = always global memory, -1 = the default, 32 KB), "belief_onchip_max"
+ *   (POMDP belief filter, read by gp_belief_enable: the beliefs stay in LDS across a launch when their two buffers,
+ *   8,192 bytes per state, take at most this many bytes and fit 60 KB beside the model blob; 0 = always the global
+ *   planes, -1 = the default, whatever fits).
  *   gp_debug_reset restores the defaults. Unknown key: GP_E_INVALID. */
 int gp_debug_set(const char* key, int64_t value);
 void gp_debug_reset(void);
