@@ -563,6 +563,13 @@ int gp_rollout_belief(gp_env* env, int K, void* obs, int32_t* actions, int32_t* 
   return env->be->rollout_belief(K, obs, actions, vec, value, rew, term, trunc, (hipStream_t)stream);
 }
 
+int gp_belief_backup(gp_env* env, int n_points, const float* points, int n_vectors, const float* alpha, float gamma,
+                     float* alpha_out, int32_t* act_out, float* value_out, void* stream) {
+  GP_REQUIRE_ENV();
+  return env->be->belief_backup(n_points, points, n_vectors, alpha, gamma, alpha_out, act_out, value_out,
+                                (hipStream_t)stream);
+}
+
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream) {
   GP_REQUIRE_ENV();
   return env->be->get_state(a, b, c, d, (hipStream_t)stream);

@@ -175,6 +175,11 @@ struct EnvBackend {
                              uint8_t* trunc, hipStream_t s) {
     return no_belief();
   }
+  // Point-based value backup (gp_belief_backup; pomdp_backup.hip): POMDP only.
+  virtual int belief_backup(int P, const float* points, int N, const float* alpha, float gamma, float* alpha_out,
+                            int32_t* act_out, float* value_out, hipStream_t s) {
+    return no_belief();
+  }
   int stats_path = -1;  // the last gp_controller_stats launch: 1 = LDS histogram, 0 = global atomics (gp_query "stats_lds")
   virtual int valid_cells(int which, int32_t* out, int cap) const { return 0; }
   virtual int metrics(double out[4]) = 0;  // (the sum of the kind's MetricSlots: gp_common.h sum_metric_slots)

@@ -42,6 +42,7 @@
 
 #include "gp_ctrl.h"
 #include "gp_internal.h"
+#include "pomdp_backup.h"
 
 namespace {
 
@@ -590,11 +591,13 @@ struct PomdpBackend : EnvBackend {
   int bel_cur = 0;                            // which of the two planes holds the beliefs
   int grid_bel = 1, grid_filt = 1;
   DevBuf b_bel[2], b_prior, b_cp, b_ent, b_alpha, b_vact;
+  PbHost pb;  // the point-based backup's tables, vectors and scratch (gp_belief_backup; pomdp_backup.hip)
 
   int build(const gp_pomdp_config* cfg);
   int belief_enable(const float* prior) override;
   int belief_disable() override {
     belief_on = belief_oc = false;
+    pb.release();
     for (DevBuf* b : {&b_bel[0], &b_bel[1], &b_prior, &b_cp, &b_ent}) (void)b->alloc(0);
     bf.bel[0] = bf.bel[1] = nullptr;
     bf.prior = nullptr;
@@ -648,6 +651,18 @@ struct PomdpBackend : EnvBackend {
     return GP_OK;
   }
   int set_belief_policy(int n_vec, const float* alpha, const int32_t* vec_action) override;
+  // gp_belief_backup: reads the model and the filter's float laws, writes only its outputs
+  int belief_backup(int P, const float* points, int N, const float* alpha, float gamma, float* alpha_out,
+                    int32_t* act_out, float* value_out, hipStream_t s) override {
+    if (int e = belief_ready("gp_belief_backup")) return e;
+    PbModel m;
+    m.S = d.S, m.A = d.A, m.O = d.O, m.Sp = d.Sp, m.Op = d.Op;
+    m.blob = d.blob;
+    m.off_obs = d.off_obs, m.off_rew = d.off_rew, m.off_term = d.off_term;
+    m.colptr = bf.colptr;
+    m.ent = bf.ent;
+    return pb.backup(m, P, points, N, alpha, gamma, alpha_out, act_out, value_out, s);
+  }
   int rollout_belief(int K, void* obs, int32_t* act, int32_t* vec, float* value, float* rew, uint8_t* term,
                      uint8_t* trunc, hipStream_t s) override {
     if (!has_reset) {
@@ -715,6 +730,8 @@ struct PomdpBackend : EnvBackend {
     else if (!strcmp(key, "belief_onchip")) *v = belief_oc;         // its beliefs stay in LDS across a launch
     else if (!strcmp(key, "belief_onchip_bytes")) *v = (int64_t)2 * d.S * EPB * 4;  // (compared with belief_onchip_max)
     else if (!strcmp(key, "belief_vectors")) *v = bf.N;             // vectors of the installed policy (0 = none)
+    else if (!strcmp(key, "backup_scratch_bytes")) *v = (int64_t)pb.scratch_bytes();  // gp_belief_backup's scratch
+    else if (!strcmp(key, "backup_tables")) *v = pb.built;          // its compressed tables are built
     else return EnvBackend::query(key, v);
     return GP_OK;
   }

@@ -16,8 +16,8 @@ from .envs import __all__ as _envs_all  # noqa: E402
 
 from .controller import controller_thresholds, population_thresholds  # noqa: E402
 from .pomdp_file import parse_pomdp  # noqa: E402
-from .belief import float_laws, parse_alpha, qmdp_vectors  # noqa: E402
+from .belief import collect_beliefs, float_laws, parse_alpha, pbvi, qmdp_vectors  # noqa: E402
 
 __all__ = list(_envs_all) + ["controller_thresholds", "population_thresholds", "parse_pomdp", "float_laws",
-                             "parse_alpha", "qmdp_vectors"]
+                             "parse_alpha", "qmdp_vectors", "collect_beliefs", "pbvi"]
 __version__ = "0.1.0"

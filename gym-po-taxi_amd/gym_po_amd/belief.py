@@ -1,6 +1,8 @@
-"""Belief-space helpers of the tabular POMDP env (pure numpy, nothing here touches the device): the float32 laws the
-on-device Bayes filter multiplies, QMDP alpha-vectors, and a reader of `pomdp-solve`'s `.alpha` files.
-`TabularPOMDPEnv.set_belief_policy` takes the vectors these return.
+"""Belief-space helpers of the tabular POMDP env: the float32 laws the on-device Bayes filter multiplies (DESIGN.md
+§6r), QMDP alpha-vectors, a reader of `pomdp-solve`'s `.alpha` files (pure numpy), and the drivers of the on-device
+point-based backup: `collect_beliefs` steps an env and gathers its beliefs, `pbvi` iterates
+`TabularPOMDPEnv.point_backup` (or any backup given) over a fixed point set. `TabularPOMDPEnv.set_belief_policy` takes
+the vectors these return.
 """
 import numpy as np
 
@@ -59,6 +61,84 @@ def qmdp_vectors(T, R, terminal=None, gamma=0.95, iters=1000):
     for _ in range(int(iters)):
         Q = r + gamma * (T @ (live * Q.max(-1)))
     return np.ascontiguousarray(Q.T)
+
+
+def _host(x):
+    """A numpy array of a torch tensor (any device) or of anything numpy takes."""
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def distinct_rows(b):
+    """The bitwise-distinct rows of float32 `b` [E, S] in lexicographic order of their bit patterns (for rows >= 0:
+    of their values), float32 [P, S]. -0 and +0 are different bits."""
+    b = np.ascontiguousarray(_host(b), dtype=np.float32)
+    if b.ndim != 2:
+        raise ValueError(f"rows must be [E, S], got shape {b.shape}")
+    return np.unique(b.view(np.uint32), axis=0).view(np.float32)
+
+
+def collect_beliefs(env, actions, K=None):
+    """The beliefs a run of `env` (a TabularPOMDPEnv after reset() and enable_belief()) passes through: the env is
+    stepped one step at a time and `env.belief` is gathered before every step. `actions`: an int [K, B] plane, stepped
+    by rollout() of one row and belief_filter() (reproducible on the numpy restatements), or the string "policy" with
+    `K`: K steps of rollout_belief(1) under the installed policy. Returns the bitwise-distinct rows among the K B
+    gathered beliefs, float32 [P, S] (numpy), in the order of `distinct_rows`. The env is left K steps further."""
+    seen = []
+    if isinstance(actions, str):
+        if actions != "policy":
+            raise ValueError(f"collect_beliefs: actions must be an int [K, B] plane or 'policy', got {actions!r}")
+        if K is None or int(K) < 1:
+            raise ValueError("collect_beliefs: 'policy' needs K >= 1")
+        for _ in range(int(K)):
+            seen.append(distinct_rows(env.belief))
+            env.rollout_belief(1, store=())
+    else:
+        a = _host(actions)
+        if a.ndim != 2 or a.shape[1] != env.num_envs or a.dtype.kind not in "iu" or a.shape[0] < 1:
+            raise ValueError(f"collect_beliefs: actions must be integers [K, B] = [K, {env.num_envs}] with K >= 1, got "
+                             f"{a.dtype} {a.shape}")
+        if K is not None and int(K) != a.shape[0]:
+            raise ValueError(f"collect_beliefs: K = {K} but the plane has {a.shape[0]} rows")
+        a = a.astype(np.int32)
+        for k in range(a.shape[0]):
+            seen.append(distinct_rows(env.belief))
+            o, _, tm, tr = env.rollout(a[k:k + 1])
+            env.belief_filter(a[k:k + 1], o, tm, tr)
+    return distinct_rows(np.concatenate(seen))
+
+
+def pbvi(env, points, gamma, sweeps, backup=None):
+    """Point-based value iteration (Pineau, Gordon & Thrun 2003) over the fixed belief set `points` [P, S]. Starts from
+    the single vector min(0, min reward) / (1 - gamma) in every state (float64, then float32): a lower bound of every
+    policy's value, so the value at every point never decreases. Each of the `sweeps` sweeps backs up every point
+    against the current set (`backup(points, alpha, gamma)` -> a dict of alpha [P, S], actions [P], value [P]; None:
+    `env.point_backup`) and replaces the set by the bitwise-distinct new vectors, keeping the first occurrence in point
+    order. Needs 0 <= gamma < 1. Returns (alpha float32 [N, S], actions int64 [N], values float32 [sweeps, P]): the
+    first two are what `set_belief_policy` takes."""
+    gamma = float(gamma)
+    if not 0.0 <= gamma < 1.0:
+        raise ValueError(f"pbvi: gamma must be in [0, 1), got {gamma}")
+    sweeps = int(sweeps)
+    if sweeps < 1:
+        raise ValueError(f"pbvi: sweeps must be >= 1, got {sweeps}")
+    S = int(env.n_states)
+    pts = points if hasattr(points, "detach") else np.ascontiguousarray(points, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != S or pts.shape[0] < 1:
+        raise ValueError(f"pbvi: points must be [P, S] = [P, {S}] with P >= 1, got {tuple(pts.shape)}")
+    if backup is None:
+        backup = env.point_backup
+    floor = min(0.0, float(np.min(env.reward))) / (1.0 - gamma)
+    alpha = np.full((1, S), floor, dtype=np.float32)
+    actions = np.zeros(1, dtype=np.int64)
+    values = []
+    for _ in range(sweeps):
+        out = backup(pts, alpha, gamma)
+        new = np.ascontiguousarray(_host(out["alpha"]), dtype=np.float32)
+        _, first = np.unique(new.view(np.uint32), axis=0, return_index=True)
+        first = np.sort(first)
+        alpha, actions = new[first], _host(out["actions"]).astype(np.int64)[first]
+        values.append(_host(out["value"]).astype(np.float32))
+    return alpha, actions, np.stack(values)
 
 
 def parse_alpha(text, S):

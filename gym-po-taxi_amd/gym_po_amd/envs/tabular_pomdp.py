@@ -326,6 +326,53 @@ class TabularPOMDPEnv(NativeVecEnv):
                 res[name] = res[name].view(torch.bool)
         return res
 
+    # ------------------------------------------------------------------ point-based backup ----
+    _BACKUP_OUTPUTS = ("alpha", "actions", "value")
+
+    def point_backup(self, points, alpha, gamma=0.95, out=None):
+        """One point-based value backup (csrc/pomdp_backup.hip; the rule is stated in
+        include/gym_po_amd.h): for every belief point the best one-step look-ahead vector over the set `alpha`.
+        `points` [P, S] (validated as set_belief validates beliefs: finite, >= 0, a positive sum per row; not
+        normalised), `alpha` [N, S] (finite, |alpha| <= 1e30; taken as float32), `gamma` in [0, 1]. Returns a dict of
+        alpha float32 [P, S], actions int32 [P] and value float32 [P] on the device; `out` may hold contiguous tensors
+        of these shapes to write into. Needs enable_belief() (the float laws live there); reads the model only."""
+        torch = _torch()
+        fn = self._ctrl_fn("gp_belief_backup")
+        S = self.n_states
+        t = points if isinstance(points, torch.Tensor) else torch.as_tensor(np.asarray(points, dtype=np.float32))
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if t.dim() != 2 or t.shape[1] != S:
+            raise ValueError(f"point_backup: points must be [P, S] = [P, {S}], got {tuple(t.shape)}")
+        if t.shape[0] and (not bool((torch.isfinite(t) & (t >= 0)).all()) or not bool((t.sum(-1) > 0).all())):
+            raise ValueError("point_backup: points must be finite and >= 0, and every row needs a positive sum")
+        al = np.ascontiguousarray(np.asarray(alpha.cpu() if isinstance(alpha, torch.Tensor) else alpha,
+                                             dtype=np.float32))
+        if al.ndim != 2 or al.shape[1] != S or al.shape[0] < 1:
+            raise ValueError(f"point_backup: alpha must be [N, S] = [N, {S}] with N >= 1, got shape {al.shape}")
+        P = t.shape[0]
+        want = {"alpha": ((P, S), torch.float32), "actions": ((P,), torch.int32), "value": ((P,), torch.float32)}
+        if out is not None and not isinstance(out, dict):
+            raise ValueError("out must be a dict of tensors by output name")
+        bufs = {}
+        for name in self._BACKUP_OUTPUTS:
+            shape, dt = want[name]
+            b = None if out is None else out.get(name)
+            if b is None:
+                b = torch.empty(shape, dtype=dt, device=self.device)
+            elif not isinstance(b, torch.Tensor):
+                raise ValueError(f"out {name}: expected a torch tensor")
+            elif tuple(b.shape) != shape or b.dtype != dt or b.device != self.device or not b.is_contiguous():
+                raise ValueError(f"out {name}: need a contiguous {dt} tensor of shape {shape} on {self.device}, got "
+                                 f"{b.dtype} {tuple(b.shape)} on {b.device} (contiguous={b.is_contiguous()})")
+            bufs[name] = b
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
+        _lib.check(fn(self._handle, P, ptr(t), al.shape[0], ctypes.c_void_p(al.ctypes.data), float(gamma),
+                      ptr(bufs["alpha"]), ptr(bufs["actions"]), ptr(bufs["value"]), self._stream()),
+                   "gp_belief_backup")
+        # (the launches read `t` on the current stream: the caching allocator hands its memory out again only to
+        # work queued behind them on that stream)
+        return bufs
+
 
 def heaven_hell_pomdp(env):
     """(T, Z, R, start, terminal, reset_obs) of a `HeavenHellGridEnv`: the same task as tables. S = 2 H W with state =

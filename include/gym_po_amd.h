@@ -544,6 +544,39 @@ int gp_set_belief_policy(gp_env* env, int n_vectors, const float* alpha, const i
 int gp_rollout_belief(gp_env* env, int K, void* obs, int32_t* actions, int32_t* vec, float* value, float* rew,
                       uint8_t* term, uint8_t* trunc, void* stream);
 
+/* ---- point-based value backup (POMDP only; every other kind: GP_E_UNSUPPORTED) ----
+ * The step of point-based value iteration (Pineau, Gordon & Thrun 2003): from belief points and a set of
+ * alpha-vectors, one new vector, its action and its value per point. Build-defined; pinned bit for bit to the numpy
+ * restatement tests/pbvi_oracle.py. The float laws Tf, Zf and the arithmetic are the filter's (above): float32, every
+ * product and every sum rounded separately (no FMA), sums sequential in ascending index from +0, the first maximiser
+ * wins (replaced only on a strict >). reward[s][a][s'] and terminal[s'] are the handle's.
+ * Rule. For a point b[S], the set alpha[N][S] and float32 gamma, for every action a:
+ *   1. acc_a(s') = sum_s fl(b[s] Tf[s][a][s'])                                   (the filter step's acc)
+ *   2. for every obs o: u(s') = terminal[s'] ? +0 : fl(Zf[a][s'][o] acc_a(s')); score_j = sum_s' fl(u(s') alpha[j][s']);
+ *      j*(a, o) = the first maximiser over j
+ *   3. w_a(s') = terminal[s'] ? +0 : sum_o fl(Zf[a][s'][o] alpha[j*(a, o)][s']), o ascending
+ *   4. for every s: r_a(s) = sum_s' fl(Tf[s][a][s'] reward[s][a][s']); h_a(s) = sum_s' fl(Tf[s][a][s'] w_a(s'));
+ *      beta_a(s) = fl(r_a(s) + fl(gamma h_a(s)))
+ *   5. v_a = sum_s fl(b[s] beta_a(s)); a* = the first maximiser over a
+ * Outputs per point: the vector beta_a*, the action a*, the value v_a*. A terminal s' is absorbing with value 0; the
+ * time limit is not part of the value.
+ * The device skips the terms with Tf == 0 or Zf == 0 and those of step 2 at a terminal s': with finite points, alpha
+ * and reward they are +-0 and an accumulator that starts at +0 is never -0, so the bits are those of the dense loop.
+ *
+ * gp_belief_backup: points float [P][S] (device; finite, as gp_belief_set takes them; not normalised), alpha float
+ *   [N][S] (host), alpha_out float [P][S], act_out int32 [P], value_out float [P] (device; each may be NULL). Reads
+ *   the model and writes only its outputs: beliefs, env state, step counter, metrics and an installed policy are
+ *   untouched. The vectors are copied before the call returns (it waits for the stream's earlier work first); the
+ *   kernels run on `stream`. P = 0 is a no-op.
+ *   GP_E_STATE without an enabled filter (the float laws live there). GP_E_INVALID, naming the fault: alpha not finite
+ *   or above 1e30 in magnitude, gamma outside [0, 1] or NaN, N < 1, N > 4,096 or N S > 2^22, P < 0 or P > 2^20, or
+ *   a scratch of 4 P A S + 2 P A O bytes above 2^30.
+ *   The scratch and three compressed tables (rows of Tf, Zf by (a, o) and by (a, s')) are built at the first call,
+ *   owned by the handle and freed by gp_belief_disable / gp_destroy; the scratch grows to the largest P seen.
+ *   gp_query: "backup_scratch_bytes", "backup_tables" (0 / 1). */
+int gp_belief_backup(gp_env* env, int n_points, const float* points, int n_vectors, const float* alpha, float gamma,
+                     float* alpha_out, int32_t* act_out, float* value_out, void* stream);
+
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
