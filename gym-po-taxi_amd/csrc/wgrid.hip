@@ -15,8 +15,15 @@
 //    i + rw_off, rw_off = H + used_t - used_pred; a prediction more than H off regenerates the window exactly
 //    (measured miss rate: tools/window_stats.py). So the step's critical path is only
 //      transitions (window word -> integer threshold compares -> LDS move table) -> granule publish ->
-//      all-gather of the G granules -> the block's resetter cells -> barrier,
-//    and the PCG64 work (~40 VALU per word) runs on the otherwise idle SIMDs during the exchange.
+//      all-gather of the G granules -> the block's resetter cells -> the next step's transitions,
+//    and the PCG64 work (~40 VALU per word) runs on the otherwise idle SIMDs during the exchange. The window's
+//    base depends only on the step's start state and the last b, so the control wave publishes it before the
+//    transitions end and the fills start as soon as the last env wave is through the window.
+//  * Resetter ranks: control-wave lane s * 8 + w holds the ballot mask of (slot s, env wave w). The exclusive
+//    scan of the popcounts is the block rank of that segment's first resetter, the scan's last lane the block's
+//    count, and the set bits of a mask are the segment's resetters in rank order: the control wave places the
+//    cells by walking mask bits (blocks of <= 1,024 envs and the slow path: the env waves place their own, from
+//    the same prefixes).
 //  * choice() words: 512 COARSE STATES S(y + 1 + 32 j) (one per env lane, a per-lane constant jump) cover the
 //    first 16384 draws after random(B); a resetter's word is one jump (<= 31 steps, LDS table) from a coarse state.
 //  * Lemire rejections (p ~ 2.4e-8 per word for 104 cells): each block checks a 62-draw slice of the choice
@@ -26,7 +33,7 @@
 //  * Outputs: the env waves stage {cell, term, trunc, wall-bump} per env (4 B) in LDS; two store waves turn a
 //    step's staging into obs (per-cell obs table), reward, terminated and truncated with 16-B non-temporal
 //    stores while the next step runs (double-buffered staging).
-// Synchronisation: one workgroup barrier per step (B2, after the exchange) plus LDS counters; cross-block only
+// Synchronisation: no workgroup barrier inside the step loop, only monotone LDS counters (WgShared); cross-block only
 // the tagged 8-B granules (agent-scope relaxed stores / polls, MI355X_MICROARCH.md "handoff" rows), each wait
 // bounded by spin_limit (GridCtl::err flags a grid that cannot make progress).
 #include <stdint.h>
@@ -100,11 +107,16 @@ constexpr int NCAND = 512;            // candidate resetter cells drawn during t
 constexpr uint32_t CAND_W = 192;      // half-words of them before the predicted block prefix
 
 struct WgShared {
-  uint64_t mask[8][EW];      // this step's resetter ballots by (slot k, env wave w)
+  // Resetter ballots by step parity, slot k and env wave w. The control wave reads step k's masks after
+  // trans_done(k) (its block count, and the mask walk that places the resetters' cells); the env waves do not read
+  // them. An env wave writes mask[k & 1] again in step k + 2's transitions, which it starts only after
+  // cells_done(k + 1); the control wave stores that after its trans_done(k + 1) wait, hence after its step-k reads
+  // (program order, the masks held in registers from the publish on). So trans_done(k + 1) -> cells_done(k + 1)
+  // precedes every write of step k + 2's masks, and no wave has to report "masks read".
+  uint64_t mask[2][8][EW];
   // monotone LDS counters: the waves never meet at a workgroup barrier inside the step loop
   uint32_t trans_done;       // env waves done with a step's transitions (EW per step)
   uint32_t cs_done;          // env waves done with a step's coarse states
-  uint32_t r2s_done;         // env waves done listing a step's resetters in r2s
   uint32_t fill_done;        // env-wave window fills (and exact regenerations) completed
   uint32_t res_done;         // env waves done taking a step's resetter cells (the staging is final)
   uint32_t st_done;          // store-wave step copies completed (SW per step)
@@ -120,7 +132,9 @@ struct WgShared {
   uint32_t R, h, u, nrp;     // block prefix, has_uint32 / uinteger at the step start, # rejected positions (slow path)
   uint32_t cbase;            // half-word of cand[0] (env-wave cells)
   uint32_t rp[MAXRP];        // slow path: rejected half-word positions, ascending
-  uint16_t r2s[4096];        // resetter rank in the block -> env slot
+  uint32_t pre[2][64];       // by step parity: exclusive prefix of the mask popcounts, entry s * EW + w = the block rank
+                             // of (slot s, env wave w)'s first resetter (published with cells_done; the env waves'
+                             // own placement paths read it before res_done, two steps before it is rewritten)
   uint16_t cand[NCAND];      // the cells of choice() half-words cbase .. cbase + NCAND - 1 (predicted block prefix)
 };
 
@@ -417,9 +431,10 @@ __device__ __forceinline__ uint32_t ctrl_slow(const WgParams& P, WgShared& sh, c
 }
 
 // ------------------------------------------------------------------ the control wave ----
-// Per step: S(x) published (sx_ready: the env waves' coarse states), the rejection check of its slice, the block's
-// reset count once the env waves' transitions are in, the granule published, S(y) and the next window's base
-// (sy_ready), the all-gather, the resetters' cells (cells_done), then the next step's S(x) = J_used(S(y)). Every
+// Per step: S(x) published (sx_ready: the env waves' coarse states), the rejection check of its slice, S(y) and the
+// next window's base (sy_ready), the block's reset count once the env waves' transitions are in, the granule
+// published, the candidate cells, the all-gather, the resetters' cells by mask walk (cells_done), then the next
+// step's S(x) = J_used(S(y)). Every
 // constant part of a jump (random(B), the block and lane offsets) is folded into per-lane / per-block tables, so
 // the chain from one exchange to the next publish is two table jumps and one per-lane jump.
 template <int NS, int NA>
@@ -470,15 +485,11 @@ __device__ __forceinline__ void wg_ctrl(const WgParams& P, WgShared& sh, const T
       rj = lemire_rejected(u, nag, thra) ? 1u : 0u;  // the buffered half is hw 0
     }
     const uint32_t rejc = wave_sum(rj);
-    WSTAMP(P, k, 6);
-    // this block's reset count, published
-    lds_wait(&sh.trans_done, (uint32_t)EW * (uint32_t)(k + 1), derr);
-    WSTAMP(P, k, 7);
-    const uint32_t cb = wave_sum(lane < NS * EW ? (uint32_t)__builtin_popcountll(sh.mask[lane >> 3][lane & 7]) : 0u);
-    uint64_t* slots = P.slots + (size_t)(ts & 1u) * 2 * G;
-    publish(P, slots, ts << 6, rejc, cb);
-    WSTAMP(P, k, 8);
-    // while the granules travel: S(y) and the next step's window, around the used predicted from the last b
+    // While the env waves run their transitions: S(y) and the next step's window base, around the used predicted
+    // from the last b. All of it depends only on Sx, bprev and h, so the env waves can start their fills as soon as
+    // the last of them is through the window. The parity buffers sy[k & 1] and rw[(k + 1) & 1] were last read in
+    // step k - 2 (slow-path placement, fill, regeneration), before every wave's trans_done(k - 1), which gather
+    // k - 1 and so this step's start lie behind.
     const u128 Sy = apply_jump(jB, Sx);
     uint32_t used_p, hp;
     words_to_draws(bprev + bias, h, used_p, hp);
@@ -492,6 +503,24 @@ __device__ __forceinline__ void wg_ctrl(const WgParams& P, WgShared& sh, const T
       lds_release();
       __hip_atomic_store(&sh.sy_ready, (uint32_t)k + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
+    WSTAMP(P, k, 6);
+    // this block's reset count, published. Lane j = s * EW + w keeps the mask of (slot s, env wave w): the exclusive
+    // scan of the popcounts is the block rank of that segment's first resetter, the scan's last lane the count.
+    lds_wait(&sh.trans_done, (uint32_t)EW * (uint32_t)(k + 1), derr);
+    WSTAMP(P, k, 7);
+    uint64_t m = lane < NS * EW ? sh.mask[k & 1][lane >> 3][lane & 7] : 0ull;
+    uint32_t ex;
+    uint32_t cb;
+    {
+      const uint32_t c = (uint32_t)__builtin_popcountll(m);
+      const uint32_t incl = wave_incl_scan(c);
+      ex = incl - c;
+      cb = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    uint64_t* slots = P.slots + (size_t)(ts & 1u) * 2 * G;
+    publish(P, slots, ts << 6, rejc, cb);
+    WSTAMP(P, k, 8);
+    sh.pre[k & 1][lane] = ex;  // (released with cells_done)
     // While the granules travel (the longest wait of a step): the cells of the choice() half-words around the block
     // prefix predicted by the last step's, so that the resetters' cells after the exchange are one LDS read each.
     // Candidate i is half-word cbase + i; cbase = 2 d0 + h, draws d0 .. d0 + NCAND / 2 - 1 (both halves each).
@@ -528,8 +557,6 @@ __device__ __forceinline__ void wg_ctrl(const WgParams& P, WgShared& sh, const T
     const uint32_t rtot = wave_sum(grej(g[0]) + grej(g[1]) + grej(g[2]) + grej(g[3]));
     const bool slow = rtot != 0 || b > 124u * (uint32_t)G;
     uint32_t used, h2;
-    // (also before cells_done when nothing is drawn: every env wave has read this step's masks)
-    lds_wait(&sh.r2s_done, (uint32_t)EW * (uint32_t)(k + 1), derr);
     if (!slow) {
       words_to_draws(b, h, used, h2);
       if (envcells && lane == 0) {  // the env waves place their own resetters (rank q -> half-word R + q)
@@ -539,10 +566,14 @@ __device__ __forceinline__ void wg_ctrl(const WgParams& P, WgShared& sh, const T
         sh.cbase = cbase;
       }
       if (cb && !envcells) {  // this block's resetters' cells: rank q takes half-word R + q
+        // The set bits of a lane's mask are its segment's resetters in rank order (slot-major, then wave, then lane):
+        // each lane walks its own bits, ranks ex, ex + 1, ...
         uint16_t* st = reinterpret_cast<uint16_t*>(L.stg(k, E));
-        for (uint32_t q = (uint32_t)lane; q < cb; q += 64u) {
-          const uint32_t hw = R + q;
-          const uint32_t slot = sh.r2s[q];
+        const uint32_t seg = (uint32_t)(lane >> 3) * 512u + (uint32_t)(lane & 7) * 64u;
+        while (m) {  // (the wave runs as many rounds as its fullest lane has bits)
+          const uint32_t slot = seg + (uint32_t)__builtin_ctzll(m);
+          m &= m - 1;
+          const uint32_t hw = R + ex++;
           uint32_t cell;
           if (hw - cbase < (uint32_t)NCAND && !(P.tmode & TM_NOCAND)) {  // (hw >= cbase >= h: never the buffered half)
             cell = sh.cand[hw - cbase];
@@ -616,7 +647,7 @@ struct Acc {
 // Slow path: place this lane's resetters exactly (ranks -> positions past the listed rejections -> words).
 template <int NS>
 __device__ __forceinline__ void wg_env_slow(const WgParams& P, WgShared& sh, const Tabs& tb, const uint64_t* CS,
-                                            int k, char* stg, uint32_t dn, const uint32_t (&pre)[NS],
+                                            int k, char* stg, uint32_t dn, const uint32_t* prew,
                                             const uint64_t (&bm)[NS], uint32_t (&ae)[NS]) {
   const int lg = threadIdx.x;
   const u128 Sy = mk128(sh.sy[k & 1][0], sh.sy[k & 1][1]);
@@ -624,7 +655,7 @@ __device__ __forceinline__ void wg_env_slow(const WgParams& P, WgShared& sh, con
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     if (!((dn >> s) & 1u)) continue;
-    uint32_t p = R + pre[s] + mbcnt(bm[s]);
+    uint32_t p = R + prew[s * EW] + mbcnt(bm[s]);
     for (uint32_t q = 0; q < n; ++q) p += sh.rp[q] <= p ? 1u : 0u;
     uint32_t word;
     if (h && p == 0) {
@@ -642,12 +673,12 @@ __device__ __forceinline__ void wg_env_slow(const WgParams& P, WgShared& sh, con
 }
 
 // Fast path (no rejection in the step's choice() words), blocks of <= 1,024 envs: this lane's resetters take
-// half-words R + rank, rank from the listing (pre + mbcnt); their cells are the control wave's candidates when inside
+// half-words R + rank, rank from the control wave's prefix (prew + mbcnt); their cells are the control wave's candidates when inside
 // its window, else drawn from the coarse states (the control wave publishes R, h, u, cbase with cells_done and draws
 // nothing after the all-gather, so its cells loop is off the step's chain).
 template <int NS>
 __device__ __forceinline__ void wg_env_cells(const WgParams& P, WgShared& sh, const Tabs& tb, const uint64_t* CS,
-                                             char* stg, uint32_t dn, const uint32_t (&pre)[NS], const uint64_t (&bm)[NS],
+                                             char* stg, uint32_t dn, const uint32_t* prew, const uint64_t (&bm)[NS],
                                              uint32_t (&ae)[NS]) {
   if (!dn) return;
   const int lg = threadIdx.x;
@@ -656,7 +687,7 @@ __device__ __forceinline__ void wg_env_cells(const WgParams& P, WgShared& sh, co
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     if (!((dn >> s) & 1u)) continue;
-    const uint32_t hw = R + pre[s] + mbcnt(bm[s]);
+    const uint32_t hw = R + prew[s * EW] + mbcnt(bm[s]);
     uint32_t cell;
     if (hw - cbase < (uint32_t)NCAND && !nocand) {  // (hw >= cbase >= h: never the buffered half)
       cell = sh.cand[hw - cbase];
@@ -756,7 +787,6 @@ __device__ __forceinline__ void wg_env(const WgParams& P, WgShared& sh, const Ta
   if (w == 0) LSTAMP(P, 7);
   uint32_t fill_target = EW;
   uint64_t bm[NS];
-  uint32_t pre[NS];
   for (int k = 0; k < K; ++k) {
     char* stg = L.stg(k, E);
     if (w == 0) WSTAMP(P, k, 41);
@@ -813,7 +843,7 @@ __device__ __forceinline__ void wg_env(const WgParams& P, WgShared& sh, const Ta
     }
     if (lane == 0) {
 #pragma unroll
-      for (int s = 0; s < NS; ++s) sh.mask[s][w] = bm[s];
+      for (int s = 0; s < NS; ++s) sh.mask[k & 1][s][w] = bm[s];
     }
 #pragma unroll
     for (int s = 0; s < NS; ++s) reinterpret_cast<uint32_t*>(stg)[s * 512 + lg] = sv[s];
@@ -828,7 +858,7 @@ __device__ __forceinline__ void wg_env(const WgParams& P, WgShared& sh, const Ta
 #pragma unroll
       for (int s = 0; s < NS; ++s) anext[s] = act[(size_t)(k + 1) * B + e0 + (size_t)s * 512 + lg];
     }
-    // ---- while the exchange runs: coarse states, resetter listing, the next step's window ----
+    // ---- while the exchange runs: coarse states, the next step's window ----
     lds_wait(&sh.sx_ready, (uint32_t)k + 1u, derr);
     if (w == 0) WSTAMP(P, k, 2);
     {
@@ -838,21 +868,11 @@ __device__ __forceinline__ void wg_env(const WgParams& P, WgShared& sh, const Ta
     lds_release();
     if (lane == 0) lds_add(&sh.cs_done, 1u);
     if (w == 0) WSTAMP(P, k, 3);
-    lds_wait(&sh.trans_done, (uint32_t)EW * (uint32_t)(k + 1), derr);  // every wave's masks; nobody reads the window now
-    {
-      const uint32_t c = lane < NS * EW ? (uint32_t)__builtin_popcountll(sh.mask[lane >> 3][lane & 7]) : 0u;
-      const uint32_t ex = wave_incl_scan(c) - c;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        pre[s] = (uint32_t)__builtin_amdgcn_readlane((int)ex, s * EW + w);
-        if ((dn >> s) & 1u) sh.r2s[pre[s] + mbcnt(bm[s])] = (uint16_t)(s * 512 + lg);
-      }
-    }
-    lds_release();
-    if (lane == 0) lds_add(&sh.r2s_done, 1u);
-    if (w == 0) WSTAMP(P, k, 4);
     if (k + 1 < K) {
-      lds_wait(&sh.sy_ready, (uint32_t)k + 1u, derr);
+      // the window is single-buffered: nobody reads it once every env wave is through its transitions
+      lds_wait(&sh.trans_done, (uint32_t)EW * (uint32_t)(k + 1), derr);
+      lds_wait(&sh.sy_ready, (uint32_t)k + 1u, derr);  // (published before the transitions ended)
+      if (w == 0) WSTAMP(P, k, 4);
       const u128 Srw = mk128(sh.rw[(k + 1) & 1][0], sh.rw[(k + 1) & 1][1]);
       if (!(tmode & TM_NOFILL)) fill_window(L.RW, jrw, jrow, fr0, nrow, Srw, lane);
       lds_release();
@@ -868,10 +888,11 @@ __device__ __forceinline__ void wg_env(const WgParams& P, WgShared& sh, const Ta
     lds_wait(&sh.cells_done, (uint32_t)k + 1u, derr);
     if (w == 0) WSTAMP(P, k, 11);
     const uint32_t fix = sh.fix[k & 1];
+    const uint32_t* prew = &sh.pre[k & 1][w];  // block ranks of this wave's first resetter per slot (control wave)
     if (fix & 1u) {
-      wg_env_slow<NS>(P, sh, tb, L.CS(k), k, stg, dn, pre, bm, ae);
+      wg_env_slow<NS>(P, sh, tb, L.CS(k), k, stg, dn, prew, bm, ae);
     } else if (envcells) {
-      wg_env_cells<NS>(P, sh, tb, L.CS(k), stg, dn, pre, bm, ae);
+      wg_env_cells<NS>(P, sh, tb, L.CS(k), stg, dn, prew, bm, ae);
     } else {
 #pragma unroll
       for (int s = 0; s < NS; ++s)
@@ -1009,7 +1030,7 @@ __global__ __launch_bounds__(TPB) void wgrid_rollout(const WgParams* __restrict_
     if (wid == EW + 1) LSTAMP(P, 6);
   }
   if (tid == EW * 64) {
-    sh.trans_done = sh.cs_done = sh.r2s_done = sh.fill_done = sh.res_done = sh.st_done = 0;
+    sh.trans_done = sh.cs_done = sh.fill_done = sh.res_done = sh.st_done = 0;
     sh.sx_ready = sh.sy_ready = sh.cells_done = sh.pro = 0;
     if (!(P.tmode & TM_OLDPRO)) sh.fill_done = EW;  // step 0's words: every env wave wrote its own before P1
     sh.fix[0] = sh.fix[1] = 0;

@@ -4,9 +4,9 @@
 
 Stamps are s_memrealtime (100 MHz, synchronous across XCDs), kept in LDS during the launch (round 6: a global store
 per stamp was waited for by later vmcnt(0) waits and stretched the phases), per block and step k < 24 (42 slots):
-  env wave 0: 0 step start, 1 transitions done, 2 S(y) seen, 3 coarse states done, 4 resetters listed,
-              5 window filled (before B2); env wave 7: 15 window filled
-  control:    6 S(y) + rejection check + window base published, 7 transitions seen, 8 granule publish,
+  env wave 0: 0 step start, 1 transitions done, 2 S(x) seen, 3 coarse states done, 4 window fill start (every
+              wave's transitions done), 5 window filled; env wave 7: 15 window filled
+  control:    6 rejection check done, S(y) + window base published, 7 transitions seen, 8 granule publish,
               9 all-gather done, 10 cells drawn (before B2), 11 after B2, 12 next state done
   store wave: 13 copy start (after B2), 14 copy issued
   every env wave w: 16 + w transitions done, 24 + w window filled (before B2), 32 + w step start
@@ -102,7 +102,7 @@ rep("step (env wave 0 start -> next start)", step)
 rep("env: transitions (0->1)", x[:, :, 1] - x[:, :, 0])
 rep("env: S(y) wait (1->2)", x[:, :, 2] - x[:, :, 1])
 rep("env: coarse states (2->3)", x[:, :, 3] - x[:, :, 2])
-rep("env: resetter listing (3->4)", x[:, :, 4] - x[:, :, 3])
+rep("env: wait for every wave's transitions (3->4)", x[:, :, 4] - x[:, :, 3])
 rep("env: window fill (4->5)", x[:, :, 5] - x[:, :, 4])
 rep("env: B2 wait (5 -> ctrl 11)", x[:, :, 11] - x[:, :, 5])
 rep("env wave 7 window done - wave 0 (15-5)", x[:, :, 15] - x[:, :, 5])
