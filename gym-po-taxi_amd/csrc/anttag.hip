@@ -92,7 +92,7 @@ struct StepOut {
 
 template <bool REPLAY>
 __device__ __forceinline__ StepOut at_env_step(const AtDev& p, const uint8_t* lds, uint32_t& u, int a, int env,
-                                               bool live, uint64_t step, float& rsum, uint32_t& eps, uint32_t& lens) {
+                                               bool live, uint64_t step, double& rsum, uint32_t& eps, uint32_t& lens) {
   const int N = p.N;
   int ant = (int)(u & 0xFFu), tgt = (int)((u >> 8) & 0xFFu);
   uint32_t el = (u >> 16) + 1u;
@@ -131,7 +131,7 @@ __device__ __forceinline__ StepOut at_env_step(const AtDev& p, const uint8_t* ld
   o.trunc = el >= (uint32_t)p.time_limit ? 1 : 0;
   u = (uint32_t)(ay * N + ax) | ((uint32_t)(ty * N + tx) << 8) | (min(el, 0xFFFFu) << 16);
   if (!live) return o;
-  rsum += o.rew;
+  rsum += (double)o.rew;
   if (o.term | o.trunc) {
     eps += 1u;
     lens += el;
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(TPB, GP_AT_WAVES) void anttag_rollout(AtDev p, int 
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   int4* wv = s_obs + wid * 64 * EPT;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(TPB) void anttag_rollout_idx(AtDev p, CtrlDev c, in
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   stage_tables(p, lds);
   __syncthreads();
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(TPB) void cf_rollout(CfDev p, int K, uint64_t step0
   __shared__ uint32_t s_cnt[WAVES];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float4* wv = s_obs + wid * 64 * 3;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, nst = 0;
   // lens is 64-bit from the thread on: one episode can be 2^29 steps long (MAX_TIME_LIMIT), so four envs of a thread
   // that end together already sum to 2^31 and two such threads wrapped a 32-bit wave sum to 0 (block_metrics' LT)
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(TPB) void cf_rollout(CfDev p, int K, uint64_t step0
         tr[i] = o.trunc;
         if (live) {
           nst += 1u;
-          rsum += o.rew;
+          rsum += (double)o.rew;
           if (o.term | o.trunc) {
             eps += 1u;
             lens += (unsigned long long)(e[i].w >> 2);

@@ -441,7 +441,7 @@ template <bool REPLAY, bool DEFER = false, int SPEC = 0>
 __device__ __forceinline__ StepOut crooms_env_step(const CrDev& p, const uint8_t* lds, int env, bool live,
                                                    uint64_t step, double a0, double a1, int ad, double& ay,
                                                    double& ax, double& vy, double& vx, uint32_t& g, int32_t& el,
-                                                   float& rsum, uint32_t& eps, uint32_t& lens, int wix = -1) {
+                                                   double& rsum, uint32_t& eps, uint32_t& lens, int wix = -1) {
   StepOut o;
   el += 1;
   Draws d;
@@ -521,7 +521,7 @@ __device__ __forceinline__ StepOut crooms_env_step(const CrDev& p, const uint8_t
   o.rew = o.term ? p.r_goal : (oob ? p.r_wall : p.r_step);
   o.trunc = el > p.time_limit ? 1 : 0;
   if (!live) return o;
-  rsum += o.rew;
+  rsum += (double)o.rew;
   if (o.term | o.trunc) {
     eps += 1u;
     lens += (uint32_t)el;
@@ -542,7 +542,7 @@ __global__ __launch_bounds__(TPB, GP_CR_WAVES) void crooms_rollout(CrDev p, int 
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   stage_tables(p, lds);
   __syncthreads();
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;
@@ -607,12 +607,13 @@ __global__ __launch_bounds__(TPB, GP_CR_WAVES) void crooms_rollout(CrDev p, int 
       }
       float r[EPT];
       uint8_t tm[EPT], tr[EPT];
+      double rdrop = 0.0;  // the step function's own sum is dropped: the rewards join rsum at the step's end (below)
 #pragma unroll
       for (int i = 0; i < EPT; ++i) {
         const int env = env0 + i;
         const bool live = env < p.B;
         StepOut o = crooms_env_step<REPLAY, false, SPEC>(p, lds, env, live, stp, a0[i], a1[i], ad[i], ay[i], ax[i],
-                                            vy[i], vx[i], g[i], el[i], rsum, eps, lens);
+                                            vy[i], vx[i], g[i], el[i], rdrop, eps, lens);
         r[i] = o.rew;
         tm[i] = o.term;
         tr[i] = o.trunc;
@@ -637,6 +638,11 @@ __global__ __launch_bounds__(TPB, GP_CR_WAVES) void crooms_rollout(CrDev p, int 
         for (int i = 0; i < EPT; ++i)
           if (env0 + i < p.B) write_obs<OK>(p, lds, env0 + i, ay[i], ax[i], g[i], (uint8_t*)obs + ob);
       }
+      // the float64 return, added where the step holds the fewest registers (inside the transition the double cost
+      // 8-16 B more scratch in the instances that spill)
+#pragma unroll
+      for (int i = 0; i < EPT; ++i)
+        if (env0 + i < p.B) rsum += (double)r[i];
     }
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
@@ -706,7 +712,7 @@ __global__ __launch_bounds__(TPB, GP_CR_CTRL_WAVES) void crooms_rollout_ctrl(
   uint8_t* const cnode = c.node;
   const int cM = c.M, cL = c.L;
   const uint32_t cNobs = (uint32_t)c.n_obs, cInv = c.inv_m;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;
@@ -1171,7 +1177,7 @@ __global__ __launch_bounds__(XT) void crooms_numpy_rollout(CrDev p, CrExact x, i
     }
   }
   // p.rp_* point at the per-env draw buffers (x.u / gi / ai / noise / wall), set by the host
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int k = 0; k < K && !sh.err; ++k) {
     const size_t off = (size_t)k * p.B;
@@ -1188,7 +1194,7 @@ __global__ __launch_bounds__(XT) void crooms_numpy_rollout(CrDev p, CrExact x, i
       double vy = p.use_velocity ? p.vy[env] : 0.0, vx = p.use_velocity ? p.vx[env] : 0.0;
       uint32_t g = x_goal(p, env);
       int32_t el = p.el[env];
-      float rs = 0.f;
+      double rs = 0.0;
       uint32_t ep = 0, ln = 0;
       o = crooms_env_step<true>(p, lds, env, true, 0, a0, a1, ad, ay, ax, vy, vx, g, el, rs, ep, ln);
     };
@@ -1260,29 +1266,28 @@ __global__ __launch_bounds__(XT) void crooms_numpy_rollout(CrDev p, CrExact x, i
     __syncthreads();
   }
   // metrics into slot 0
-  __shared__ float m_r;
-  __shared__ unsigned long long m_e, m_l, m_n;
-  if (t == 0) { m_r = 0.f; m_e = m_l = m_n = 0; }
-  __syncthreads();
+  // (float64 return and 64-bit counters from the wave shuffle on: the law of gp_metrics; the waves' partials are
+  // added in wave order, so the value does not depend on which wave arrives first)
+  __shared__ double m_r[XT / 64];
+  __shared__ unsigned long long m_e[XT / 64], m_l[XT / 64], m_n[XT / 64];
+  unsigned long long eps64 = eps, lens64 = lens, nst64 = nst;
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
+    eps64 += __shfl_xor(eps64, d, 64);
+    lens64 += __shfl_xor(lens64, d, 64);
+    nst64 += __shfl_xor(nst64, d, 64);
   }
-  if ((t & 63) == 0) {
-    atomicAdd(&m_r, rsum);
-    atomicAdd(&m_e, (unsigned long long)eps);
-    atomicAdd(&m_l, (unsigned long long)lens);
-    atomicAdd(&m_n, (unsigned long long)nst);
-  }
+  if ((t & 63) == 0) { m_r[t >> 6] = rsum; m_e[t >> 6] = eps64; m_l[t >> 6] = lens64; m_n[t >> 6] = nst64; }
   __syncthreads();
   if (t == 0) {
+    double r = 0.0;
+    unsigned long long e = 0, l = 0, n = 0;
+    for (int w = 0; w < XT / 64; ++w) { r += m_r[w]; e += m_e[w]; l += m_l[w]; n += m_n[w]; }
     MetricSlot& m = p.mslot[0];
-    m.return_sum += (double)m_r;
-    m.episodes += m_e;
-    m.length_sum += m_l;
-    m.env_steps += m_n;
+    m.return_sum += r;
+    m.episodes += e;
+    m.length_sum += l;
+    m.env_steps += n;
     x.rng->s_hi = sh.st_hi;
     x.rng->s_lo = sh.st_lo;
     x.rng->has_u32 = sh.has_u32;
@@ -2309,7 +2314,7 @@ __global__ __launch_bounds__(XGT) void xg_dry(CrDev p, XgFlags fd, const void* _
         g = x_goal(p, env);
       }
       int32_t el = p.el[env];
-      float rs = 0.f;
+      double rs = 0.0;
       uint32_t ep = 0, ln = 0;
       const StepOut o = crooms_env_step<true>(p, lds, env, true, 0, a0, a1, ad, ay, ax, vy, vx, g, el, rs, ep, ln);
       f = o.oob != 0;
@@ -2333,7 +2338,7 @@ __global__ __launch_bounds__(XGT) void xg_step(CrDev p, XgFlags fd, XgFlags fs, 
   const int sb0 = blockIdx.x * SPB;
   uint32_t wpre = xg_prefix(fd.c, sb0);  // (its block sum syncs the table copy too)
   XSTAMP(3, 1);
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
 #pragma unroll
   for (int b = 0; b < SPB; ++b) {
@@ -2371,27 +2376,30 @@ __global__ __launch_bounds__(XGT) void xg_step(CrDev p, XgFlags fd, XgFlags fs, 
   }
   XSTAMP(3, 2);
   // episode statistics: block reduction, one set of atomics per workgroup
-  __shared__ float m_r[XGW];
-  __shared__ uint32_t m_e[XGW], m_l[XGW], m_n[XGW];
+  // (float64 return and 64-bit counters from the wave shuffle on: the law of gp_metrics; the blocks' totals meet in
+  // the slot in the order their atomics land)
+  __shared__ double m_r[XGW];
+  __shared__ unsigned long long m_e[XGW], m_l[XGW], m_n[XGW];
+  unsigned long long eps64 = eps, lens64 = lens, nst64 = nst;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
+    eps64 += __shfl_xor(eps64, d, 64);
+    lens64 += __shfl_xor(lens64, d, 64);
+    nst64 += __shfl_xor(nst64, d, 64);
   }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) { m_r[wv] = rsum; m_e[wv] = eps; m_l[wv] = lens; m_n[wv] = nst; }
+  if (lane == 0) { m_r[wv] = rsum; m_e[wv] = eps64; m_l[wv] = lens64; m_n[wv] = nst64; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float r = 0.f;
-    uint32_t ee = 0, l = 0, nn = 0;
+    double r = 0.0;
+    unsigned long long ee = 0, l = 0, nn = 0;
     for (int i = 0; i < XGW; ++i) { r += m_r[i]; ee += m_e[i]; l += m_l[i]; nn += m_n[i]; }
     MetricSlot& m = p.mslot[blockIdx.x % p.nslot];  // (one slot for every block serialised up to 6 us of atomics)
-    atomicAdd(&m.return_sum, (double)r);
-    atomicAdd(&m.episodes, (unsigned long long)ee);
-    atomicAdd(&m.length_sum, (unsigned long long)l);
-    atomicAdd(&m.env_steps, (unsigned long long)nn);
+    atomicAdd(&m.return_sum, r);
+    atomicAdd(&m.episodes, ee);
+    atomicAdd(&m.length_sum, l);
+    atomicAdd(&m.env_steps, nn);
   }
   XSTAMP(3, 7);
 }

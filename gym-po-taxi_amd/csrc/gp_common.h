@@ -157,13 +157,15 @@ struct StepOut {
 };
 
 // A block's metrics into its own slot p.mslot[blockIdx.x] (no other block writes it), p being the kind's XxDev: wave
-// shuffles, the waves' partials through LDS, thread 0 adds them up. LT: the type of the per-thread length sum
-// (Car-Flag's is 64-bit).
+// shuffles, the waves' partials through LDS, thread 0 adds them up. The law of gp_metrics (include/gym_po_amd.h):
+// rsum is the thread's float64 sum of its float32 rewards and stays float64 through the shuffles, the LDS partials
+// and the slot's +=; the three counters are 32-bit per thread (LT: Car-Flag's length sum is 64-bit) and 64-bit from
+// the wave shuffle on, so a block's totals do not wrap at 2^32 env-steps a launch.
 template <int NW, class Dev, class LT>
-__device__ void block_metrics(const Dev& p, float rsum, uint32_t eps, LT lens, uint32_t nst) {
-  __shared__ float s_r[NW];
-  __shared__ uint32_t s_e[NW], s_n[NW];
-  __shared__ LT s_l[NW];
+__device__ void block_metrics(const Dev& p, double rsum, uint32_t eps32, LT lens_t, uint32_t nst32) {
+  __shared__ double s_r[NW];
+  __shared__ unsigned long long s_e[NW], s_l[NW], s_n[NW];
+  unsigned long long eps = eps32, lens = lens_t, nst = nst32;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
@@ -175,11 +177,11 @@ __device__ void block_metrics(const Dev& p, float rsum, uint32_t eps, LT lens, u
   if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float r = 0.f;
+    double r = 0.0;
     unsigned long long e = 0, l = 0, n = 0;
     for (int w = 0; w < NW; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
     MetricSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
+    m.return_sum += r;
     m.episodes += e;
     m.length_sum += l;
     m.env_steps += n;

@@ -488,10 +488,13 @@ __device__ __noinline__ uint32_t scan_accepted(const GridDev* __restrict__ gp, c
   return a;
 }
 
-// Per-block metrics (episode count / return / length / env-steps) into the block's own slot.
-__device__ void add_metrics(const GridDev& p, float rsum, uint32_t eps, uint32_t lens, uint32_t nsteps) {
-  __shared__ float s_r[TPB / 64];
-  __shared__ uint32_t s_e[TPB / 64], s_l[TPB / 64], s_n[TPB / 64];
+// Per-block metrics (episode count / return / length / env-steps) into the block's own slot. rsum is the thread's
+// float64 sum of its float32 rewards and stays float64 to the slot; the counters are 64-bit from the wave shuffle on
+// (the law of gp_metrics, include/gym_po_amd.h).
+__device__ void add_metrics(const GridDev& p, double rsum, uint32_t eps32, uint32_t lens32, uint32_t nsteps32) {
+  __shared__ double s_r[TPB / 64];
+  __shared__ unsigned long long s_e[TPB / 64], s_l[TPB / 64], s_n[TPB / 64];
+  unsigned long long eps = eps32, lens = lens32, nsteps = nsteps32;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
@@ -503,10 +506,11 @@ __device__ void add_metrics(const GridDev& p, float rsum, uint32_t eps, uint32_t
   if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nsteps; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float r = 0; uint32_t e = 0, l = 0, n = 0;
+    double r = 0.0;
+    unsigned long long e = 0, l = 0, n = 0;
     for (int w = 0; w < TPB / 64; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
     MetricSlot& m = p.mslot[blockIdx.x];
-    m.return_sum += (double)r;
+    m.return_sum += r;
     m.episodes += e;
     m.length_sum += l;
     m.env_steps += n;
@@ -598,7 +602,7 @@ __global__ __launch_bounds__(TPB) void grid_step_numpy(GridDev p, const int32_t*
   uint32_t nae[4];
   int ag[4], gl[4];
   uint32_t c = 0, fm = 0;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -614,7 +618,7 @@ __global__ __launch_bounds__(TPB) void grid_step_numpy(GridDev p, const int32_t*
     c += f;
     fm |= (f ? 1u : 0u) << i;
     if (valid) {
-      rsum += t.rew;
+      rsum += (double)t.rew;
       nst += 1;
       if (f) { eps += 1; lens += (uint32_t)t.elapsed; }
     }
@@ -1643,7 +1647,7 @@ template <int OK, int QPT, int NA, bool STG, bool SMALL>
 __device__ __forceinline__ void fused_env(const GridDev& p_in, FusedShared& sh, const uint64_t* s_thr,
                                           const LTabs& tb, char* stg, int K, const int32_t* __restrict__ act,
                                           void* __restrict__ obs, float* __restrict__ rew,
-                                          uint8_t* __restrict__ term, uint8_t* __restrict__ trunc, float& rsum,
+                                          uint8_t* __restrict__ term, uint8_t* __restrict__ trunc, double& rsum,
                                           uint32_t& eps, uint32_t& lens, uint32_t& nst) {
   const GridDev& p = p_in;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1810,7 +1814,7 @@ __device__ __forceinline__ void fused_env(const GridDev& p_in, FusedShared& sh, 
         if (f && fixed_goal >= 0) gl[q][i] = fixed_goal;
         if constexpr (!GP_ACC) {
           if (valid) {
-            rsum += rw;
+            rsum += (double)rw;
             nst += 1;
           }
           if (f) {
@@ -1991,7 +1995,9 @@ __device__ __forceinline__ void fused_env(const GridDev& p_in, FusedShared& sh, 
     const uint32_t steps = nv * (uint32_t)K;
     lens += steps;
     nst += steps;
-    rsum += (float)ngoal * r_goal + (float)nwall * r_wall + (float)(steps - ngoal - nwall) * r_step;
+    // counts times float32 rewards, formed once per thread per launch in float64 (each product is exact)
+    rsum += (double)ngoal * (double)r_goal + (double)nwall * (double)r_wall +
+            (double)(steps - ngoal - nwall) * (double)r_step;
   }
 #pragma unroll
   for (int q = 0; q < QPT; ++q) {
@@ -2474,7 +2480,7 @@ __global__ __launch_bounds__(FTPB) void grid_rollout_numpy(GridDev p_in, int K, 
     __syncthreads();
     LSTAMP(1);
   }
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   if (wid == FENVW) {
     __builtin_amdgcn_s_setprio(3);  // the exchange is on every step's critical path
@@ -2490,28 +2496,30 @@ __global__ __launch_bounds__(FTPB) void grid_rollout_numpy(GridDev p_in, int K, 
     fused_env<OK, QPT, NA, STG, SMALL>(p, sh, s_thr, tb, stg, K, act, obs, rew, term, trunc, rsum, eps, lens, nst);
   }
   LSTAMP(2);
-  // metrics (the control wave contributes zeros)
+  // metrics (the control wave contributes zeros): float64 return and 64-bit counters from the wave shuffle on
+  unsigned long long eps64 = eps, lens64 = lens, nst64 = nst;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
-    eps += __shfl_xor(eps, d, 64);
-    lens += __shfl_xor(lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
+    eps64 += __shfl_xor(eps64, d, 64);
+    lens64 += __shfl_xor(lens64, d, 64);
+    nst64 += __shfl_xor(nst64, d, 64);
   }
-  __shared__ float m_r[FWAVES];
-  __shared__ uint32_t m_e[FWAVES], m_l[FWAVES], m_n[FWAVES];
-  if (lane == 0) { m_r[wid] = rsum; m_e[wid] = eps; m_l[wid] = lens; m_n[wid] = nst; }
+  __shared__ double m_r[FWAVES];
+  __shared__ unsigned long long m_e[FWAVES], m_l[FWAVES], m_n[FWAVES];
+  if (lane == 0) { m_r[wid] = rsum; m_e[wid] = eps64; m_l[wid] = lens64; m_n[wid] = nst64; }
   __syncthreads();
   if (tid == 0) {
-    float rr = 0; uint32_t e = 0, l = 0, n = 0;
+    double rr = 0.0;
+    unsigned long long e = 0, l = 0, n = 0;
     for (int w = 0; w < FWAVES; ++w) { rr += m_r[w]; e += m_e[w]; l += m_l[w]; n += m_n[w]; }
     // this block's own slot: fire-and-forget adds (a load-modify-store put two memory round trips on
     // the end of every launch)
     MetricSlot& m = p.mslot[blockIdx.x];
-    atomicAdd(&m.return_sum, (double)rr);
-    atomicAdd(&m.episodes, (unsigned long long)e);
-    atomicAdd(&m.length_sum, (unsigned long long)l);
-    atomicAdd(&m.env_steps, (unsigned long long)n);
+    atomicAdd(&m.return_sum, rr);
+    atomicAdd(&m.episodes, e);
+    atomicAdd(&m.length_sum, l);
+    atomicAdd(&m.env_steps, n);
   }
   LSTAMP(3);
 }
@@ -2535,7 +2543,7 @@ __device__ __forceinline__ void counter_env_step(const GridDev& p, const TB& tb,
                                                  uint32_t& lens) {
   Trans t = transition(p, tb, ae, goal, a, k53, thr);
   int agent = t.agent, g = goal, el = t.elapsed;
-  rsum += t.rew;
+  rsum += t.rew;  // (the callers pass a zeroed float per env-step and add it to their float64 sum)
   if (t.term | t.trunc) {
     eps += 1;
     lens += (uint32_t)el;
@@ -2581,7 +2589,7 @@ __global__ __launch_bounds__(TPB) void grid_rollout_counter(GridDev p, int K, ui
 #pragma unroll
     for (int i = 0; i < 4; ++i) g4[i] = p.fixed_goal;
   }
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   const size_t ow = (size_t)p.obs_width * ((OK == GP_OBS_HANSEN_VEC || OK == GP_OBS_WINDOW) ? 1 : 4);
   for (int k = 0; k < K; ++k) {
@@ -2608,7 +2616,7 @@ __global__ __launch_bounds__(TPB) void grid_rollout_counter(GridDev p, int K, ui
       uint32_t e1 = 0, l1 = 0;  // enter the metrics, as in grid_step_numpy
       counter_env_step<OK>(p, tb, s_thr, ae4[i], g4[i], a4[i], k53, gi, ai, r[i], tm[i], tr[i], r1, e1, l1);
       if (env < p.B) {
-        rsum += r1;
+        rsum += (double)r1;
         eps += e1;
         lens += l1;
         nst += 1;
@@ -2684,7 +2692,7 @@ __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDe
     }
     ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
   }
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int k = 0; k < K; ++k) {
     const size_t off = (size_t)k * p.B;
@@ -2713,7 +2721,7 @@ __global__ __launch_bounds__(TPB) void grid_rollout_controller(GridDev p, CtrlDe
       nd[i] = (tm[i] | tr[i]) ? (uint8_t)0 : (uint8_t)ctrl_node(j, a, c.M);  // episode end: node 0
       ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
       if (env < p.B) {
-        rsum += r1;
+        rsum += (double)r1;
         eps += e1;
         lens += l1;
         nst += 1;
@@ -2758,9 +2766,11 @@ struct PopDev {
 
 // Per-block scores into the block's own slot: per-thread double sums, reduced in double (wave shuffles, then the
 // waves' partials in thread order), plain += (no other block touches the slot; launches on a stream are ordered).
-__device__ void add_scores(const PopDev& q, double rs, double ds, uint32_t eps, uint32_t lens, uint32_t nsteps) {
+__device__ void add_scores(const PopDev& q, double rs, double ds, uint32_t eps32, uint32_t lens32,
+                           uint32_t nsteps32) {
   __shared__ double s_r[TPB / 64], s_d[TPB / 64];
-  __shared__ uint32_t s_e[TPB / 64], s_l[TPB / 64], s_n[TPB / 64];
+  __shared__ unsigned long long s_e[TPB / 64], s_l[TPB / 64], s_n[TPB / 64];
+  unsigned long long eps = eps32, lens = lens32, nsteps = nsteps32;  // 64-bit from the wave shuffle on
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rs += __shfl_xor(rs, d, 64);
@@ -2773,7 +2783,8 @@ __device__ void add_scores(const PopDev& q, double rs, double ds, uint32_t eps, 
   if (lane == 0) { s_r[wid] = rs; s_d[wid] = ds; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nsteps; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double r = 0, dd = 0; uint32_t e = 0, l = 0, n = 0;
+    double r = 0, dd = 0;
+    unsigned long long e = 0, l = 0, n = 0;
     for (int w = 0; w < TPB / 64; ++w) { r += s_r[w]; dd += s_d[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
     PopSlot& m = q.slots[blockIdx.x];
     m.return_sum += r;
@@ -2832,7 +2843,7 @@ __global__ __launch_bounds__(TPB) void grid_rollout_population(GridDev p, PopDev
     ob[i] = obs_value<OK>(p, tb, (int)(ae4[i] & 0xFFFF), g4[i]);
     w4[i] = q.W[ae4[i] >> 16];  // (elapsed is 16 bits: inside the 65,536-entry table)
   }
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   double grs = 0., gds = 0.;  // this thread's share of its group's return and discounted return
   for (int k = 0; k < K; ++k) {
@@ -2863,7 +2874,7 @@ __global__ __launch_bounds__(TPB) void grid_rollout_population(GridDev p, PopDev
       const bool ended = (tm[i] | tr[i]) != 0;
       const float dterm = __fmul_rn(w4[i], r[i]);  // one rounding, never contracted with the add below
       if (live) {
-        rsum += r1;
+        rsum += (double)r1;
         eps += e1;
         lens += l1;
         nst += 1;

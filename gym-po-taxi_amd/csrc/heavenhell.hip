@@ -85,7 +85,7 @@ __device__ __forceinline__ uint32_t hh_reset_word(const HhDev& p, const uint8_t*
 }
 
 __device__ __forceinline__ StepOut hh_env_step(const HhDev& p, const uint8_t* lds, uint32_t& st, int a, int env,
-                                               bool live, uint64_t step, float& rsum, uint32_t& eps, uint32_t& lens) {
+                                               bool live, uint64_t step, double& rsum, uint32_t& eps, uint32_t& lens) {
   int cell = (int)(st & 0xFFu);
   const uint32_t side = (st >> 8) & 1u;
   uint32_t e1 = (st >> 16) + 1u;
@@ -120,7 +120,7 @@ __device__ __forceinline__ StepOut hh_env_step(const HhDev& p, const uint8_t* ld
   if (o.term) o.rew = ((f & F_RIGHT) ? 1u : 0u) == side ? r_heaven : r_hell;
   o.trunc = e1 >= (uint32_t)p.time_limit ? 1 : 0;
   if (!live) return o;  // a padding lane: its word is never stored and counts for nothing
-  rsum += o.rew;
+  rsum += (double)o.rew;
   if (o.term | o.trunc) {
     if (!slippery) {
       const Philox4 z = hh_block(p, env, step, TAG);
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(TPB) void hh_rollout(HhDev p, CtrlDev c, int K, uin
   }
   __syncthreads();
   const uint32_t* cthr = CL ? reinterpret_cast<const uint32_t*>(lds + c.lds_off) : c.thr;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;

@@ -82,7 +82,7 @@ __device__ __forceinline__ uint32_t pd_start(const PdDev& p, const uint32_t* m, 
 // Every index is in bounds by construction: a in [0, A) by the clamp, s < S by the state word's provenance (a clamped
 // count, set_state's clamp, or word 0 of a padding lane), s' < S and obs < O by the clamp of the counts.
 __device__ __forceinline__ StepOut pd_env_step(const PdDev& p, const uint32_t* m, uint32_t& st, int32_t& ob, int a,
-                                               int env, bool live, uint64_t step, float& rsum, uint32_t& eps,
+                                               int env, bool live, uint64_t step, double& rsum, uint32_t& eps,
                                                uint32_t& lens) {
   const uint32_t S = (uint32_t)p.S, A = (uint32_t)p.A, O = (uint32_t)p.O;
   const int Sp = p.Sp, Op = p.Op;
@@ -99,7 +99,7 @@ __device__ __forceinline__ StepOut pd_env_step(const PdDev& p, const uint32_t* m
   o.term = reinterpret_cast<const uint8_t*>(m + p.off_term)[s1] ? 1 : 0;
   o.trunc = e1 >= (uint32_t)p.time_limit ? 1 : 0;
   if (!live) return o;  // a padding lane: its word is never stored and counts for nothing
-  rsum += o.rew;
+  rsum += (double)o.rew;
   // one obs search for both ends of the step: the row and the draw are chosen first
   const uint32_t* orow = m + p.off_obs + ((uint32_t)a * S + s1) * (uint32_t)Op;
   uint32_t y = z.x[1] >> 1;
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(TPB) void pd_rollout(PdDev p, CtrlDev c, int K, uin
   const uint32_t* m = TL ? reinterpret_cast<const uint32_t*>(lds) : p.blob;
   const uint32_t* cthr = CL ? reinterpret_cast<const uint32_t*>(lds + c.lds_off) : c.thr;
   const uint32_t lreal = (uint32_t)(p.A * c.M);  // a controller row's entries before its padding
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(TPB) void pd_rollout_belief(PdDev p, BfDev f, int K
   const uint32_t* m = TL ? reinterpret_cast<const uint32_t*>(lds) : p.blob;
   float* lb = reinterpret_cast<float*>(lds + bel_off);
   const size_t half = (size_t)p.S * EPB;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;

@@ -80,7 +80,7 @@ __device__ __forceinline__ int32_t rs_obs(const RsDev& p, uint32_t cm) {
 }
 
 __device__ __forceinline__ StepOut rs_env_step(const RsDev& p, const uint8_t* lds, uint32_t& cm, uint32_t& el, int a,
-                                               int env, bool live, uint64_t step, float& rsum, uint32_t& eps,
+                                               int env, bool live, uint64_t step, double& rsum, uint32_t& eps,
                                                uint32_t& lens) {
   const uint32_t* thr = reinterpret_cast<const uint32_t*>(lds);
   const uint8_t* rock_at = lds + p.off_rock;
@@ -118,7 +118,7 @@ __device__ __forceinline__ StepOut rs_env_step(const RsDev& p, const uint8_t* ld
   o.trunc = e1 >= (uint32_t)p.time_limit ? 1 : 0;
   const bool done = o.term | o.trunc;
   if (!live) return o;
-  rsum += o.rew;
+  rsum += (double)o.rew;
   if (a >= A_CHECK || done) {  // the only users of the step's block
     const Philox4 z = rs_block(p, env, step, TAG);
     if (done) {
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(TPB) void rs_rollout(RsDev p, CtrlDev c, int K, uin
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   stage_tables(p, lds);
   __syncthreads();
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     const int env0 = tile * EPB + threadIdx.x * EPT;

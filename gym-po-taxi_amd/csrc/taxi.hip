@@ -121,7 +121,7 @@ __device__ __forceinline__ uint32_t draw_pd(const TaxiDev& p, int env, uint64_t 
 // One env-step of TaxiVecEnv.step (extended_taxi.py:244-287) on the packed state `u`.
 template <bool REPLAY>
 __device__ __forceinline__ StepOut taxi_env_step(const TaxiDev& p, const uint8_t* lds, uint32_t& u, int a, int env,
-                                                 bool live, uint64_t step, float& rsum, uint32_t& eps,
+                                                 bool live, uint64_t step, double& rsum, uint32_t& eps,
                                                  uint32_t& lens) {
   uint32_t s = u & 0xFFFu, nd = (u >> 12) & 0xFu, el = (u >> 16) + 1u;  // elapsed += 1 (:245)
   // numpy negative indexing of ACTIONS_YX[actions]: -5..-2 are the moves, -1 moves (0,0) but is not
@@ -139,7 +139,7 @@ __device__ __forceinline__ StepOut taxi_env_step(const TaxiDev& p, const uint8_t
   nd = min(nd, 15u);                          // the 4-bit field saturates (set_state can store 15): never into elapsed
   o.trunc = (el > (uint32_t)p.time_limit) ? 1 : 0;
   if (!live) return o;                        // padding lane of a ragged batch: no draws, no metrics
-  rsum += o.rew;
+  rsum += (double)o.rew;
   if (goal && !(o.term | o.trunc)) {          // task completed, episode continues (:281-284)
     const uint32_t pd = draw_pd<REPLAY>(p, env, step);
     s = (s / (uint32_t)p.lpl) * (uint32_t)p.lpl + pd;  // encode(r, c, p, d): taxi cell kept
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(TPB) void taxi_rollout(TaxiDev p, int K, uint64_t s
   stage_tables(p, lds);
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   const uint16_t* obs_of = l_obs(lds, p);
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(TPB) void taxi_rollout_ctrl(TaxiDev p, CtrlDev c, i
   __syncthreads();
   const uint32_t* cthr = CL ? reinterpret_cast<const uint32_t*>(lds + c.lds_off) : c.thr;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   const uint16_t* obs_of = l_obs(lds, p);
   const uint32_t lreal = (uint32_t)(NACT * c.M);  // entries of a row before its padding to 16-B quads
@@ -860,7 +860,7 @@ __global__ __launch_bounds__(NP_TPB) void taxi_np_kernel(TaxiDev p, TaxiNpDev q,
                  (const uint16_t*)(mt + q.off_cat), mt + q.off_flip, etab};
   const uint16_t* obs_of = l_obs(lds, p);
   const int B = p.B, ntile = (B + NP_TPB - 1) / NP_TPB;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   const int steps = K > 0 ? K : 1;
   for (int k = 0; k < steps; ++k) {
@@ -888,7 +888,7 @@ __global__ __launch_bounds__(NP_TPB) void taxi_np_kernel(TaxiDev p, TaxiNpDev q,
         rew[off + env] = r;
         term[off + env] = dterm ? 1 : 0;
         trunc[off + env] = dtrunc ? 1 : 0;
-        rsum += r;
+        rsum += (double)r;
         nst += 1u;
         ftc = goal && !(dterm || dtrunc);
         frs = dterm || dtrunc;
@@ -993,10 +993,14 @@ __device__ __forceinline__ uint64_t npg_scan64(uint64_t x, uint64_t& tot) {
   return base + v - x;
 }
 
-// Metrics of a block into slot (block mod slots), atomically (more blocks than slots).
-__device__ void npg_metrics(const TaxiDev& p, int slots, float rsum, uint32_t eps, uint32_t lens, uint32_t nst) {
-  __shared__ float s_r[WAVES];
-  __shared__ uint32_t s_e[WAVES], s_l[WAVES], s_n[WAVES];
+// Metrics of a block into slot (block mod slots), atomically (more blocks than slots). The return is float64 and the
+// counters 64-bit from the wave shuffle on, as in block_metrics; the blocks' totals meet in the slot in the order
+// their atomics land, so the last bits of return_sum may differ between runs, inside the bound of gp_metrics.
+__device__ void npg_metrics(const TaxiDev& p, int slots, double rsum, uint32_t eps32, uint32_t lens32,
+                            uint32_t nst32) {
+  __shared__ double s_r[WAVES];
+  __shared__ unsigned long long s_e[WAVES], s_l[WAVES], s_n[WAVES];
+  unsigned long long eps = eps32, lens = lens32, nst = nst32;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
@@ -1008,11 +1012,11 @@ __device__ void npg_metrics(const TaxiDev& p, int slots, float rsum, uint32_t ep
   if (lane == 0) { s_r[wid] = rsum; s_e[wid] = eps; s_l[wid] = lens; s_n[wid] = nst; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float r = 0.f;
+    double r = 0.0;
     unsigned long long e = 0, l = 0, n = 0;
     for (int w = 0; w < WAVES; ++w) { r += s_r[w]; e += s_e[w]; l += s_l[w]; n += s_n[w]; }
     MetricSlot& m = p.mslot[blockIdx.x % (unsigned)slots];
-    atomicAdd(&m.return_sum, (double)r);
+    atomicAdd(&m.return_sum, r);
     atomicAdd(&m.episodes, e);
     atomicAdd(&m.length_sum, l);
     atomicAdd(&m.env_steps, n);
@@ -1028,7 +1032,7 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass1(TaxiDev p, TaxiNpDev q, Np
   if (!RESET) stage_tables(p, lds);
   __syncthreads();
   const int tile = blockIdx.x, env0 = tile * EPB + threadIdx.x * EPT;
-  float rsum = 0.f;
+  double rsum = 0.0;
   uint32_t eps = 0, lens = 0, nst = 0;
   bool ftc[EPT], frs[EPT];
   if (RESET) {
@@ -1062,7 +1066,7 @@ __global__ __launch_bounds__(TPB) void taxi_npg_pass1(TaxiDev p, TaxiNpDev q, Np
       const bool dterm = nd == (uint32_t)p.num_passengers, dtrunc = el > (uint32_t)p.time_limit;
       tm[i] = dterm ? 1 : 0;
       tr[i] = dtrunc ? 1 : 0;
-      rsum += r[i];
+      rsum += (double)r[i];
       nst += 1u;
       ftc[i] = goal && !(dterm || dtrunc);
       frs[i] = dterm || dtrunc;

@@ -1049,33 +1049,38 @@ __global__ __launch_bounds__(TPB) void wgrid_rollout(const WgParams* __restrict_
     wg_env<NS, NA>(P, sh, tb, L, dyn, act, K, acc, obs, rew, term, trunc);
   }
   // episode statistics of the launch (env waves; the others contribute zeros)
-  float rsum = 0.f;
-  uint32_t nst = 0;
+  // (counts times float32 rewards, formed once per thread in float64, each product exact; float64 return and 64-bit
+  // counters from the wave shuffle on: the law of gp_metrics)
+  double rsum = 0.0;
+  unsigned long long eps64 = 0, lens64 = 0, nst64 = 0;
   if (wid < EW) {
     const uint32_t steps = (uint32_t)(NS * K);
     acc.lens += steps;
-    nst = steps;
-    rsum = (float)acc.ngoal * P.r_goal + (float)acc.nwall * P.r_wall + (float)(steps - acc.ngoal - acc.nwall) * P.r_step;
+    eps64 = acc.eps;
+    lens64 = acc.lens;
+    nst64 = steps;
+    rsum = (double)acc.ngoal * (double)P.r_goal + (double)acc.nwall * (double)P.r_wall +
+           (double)(steps - acc.ngoal - acc.nwall) * (double)P.r_step;
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     rsum += __shfl_xor(rsum, d, 64);
-    acc.eps += __shfl_xor(acc.eps, d, 64);
-    acc.lens += __shfl_xor(acc.lens, d, 64);
-    nst += __shfl_xor(nst, d, 64);
+    eps64 += __shfl_xor(eps64, d, 64);
+    lens64 += __shfl_xor(lens64, d, 64);
+    nst64 += __shfl_xor(nst64, d, 64);
   }
-  __shared__ float m_r[NWAVES];
-  __shared__ uint32_t m_e[NWAVES], m_l[NWAVES], m_n[NWAVES];
+  __shared__ double m_r[NWAVES];
+  __shared__ unsigned long long m_e[NWAVES], m_l[NWAVES], m_n[NWAVES];
   if (lane == 0) {
     m_r[wid] = rsum;
-    m_e[wid] = acc.eps;
-    m_l[wid] = acc.lens;
-    m_n[wid] = nst;
+    m_e[wid] = eps64;
+    m_l[wid] = lens64;
+    m_n[wid] = nst64;
   }
   __syncthreads();
   if (tid == 0) {
-    float rr = 0;
-    uint32_t e = 0, l = 0, n = 0;
+    double rr = 0.0;
+    unsigned long long e = 0, l = 0, n = 0;
     for (int w = 0; w < NWAVES; ++w) {
       rr += m_r[w];
       e += m_e[w];
@@ -1083,10 +1088,10 @@ __global__ __launch_bounds__(TPB) void wgrid_rollout(const WgParams* __restrict_
       n += m_n[w];
     }
     MetricSlot& m = P.mslot[blockIdx.x];
-    atomicAdd(&m.return_sum, (double)rr);
-    atomicAdd(&m.episodes, (unsigned long long)e);
-    atomicAdd(&m.length_sum, (unsigned long long)l);
-    atomicAdd(&m.env_steps, (unsigned long long)n);
+    atomicAdd(&m.return_sum, rr);
+    atomicAdd(&m.episodes, e);
+    atomicAdd(&m.length_sum, l);
+    atomicAdd(&m.env_steps, n);
   }
 #ifdef GP_STAMPS
   __syncthreads();

@@ -605,7 +605,27 @@ int gp_set_replay(gp_env* env, const void* u, const void* i0, const void* i1, co
 int gp_valid_cells(const gp_env* env, int which, int32_t* out, int cap);
 
 /* On-device episode statistics since the last gp_reset (syncs): {episodes, return_sum,
- * length_sum, env_steps}. */
+ * length_sum, env_steps}.
+ *
+ * The law of return_sum. It is the sum of the float32 rewards of all env-steps since gp_reset, accumulated in float64
+ * from the thread on: each thread adds its rewards into a double ((double)rew, K steps x its envs x every tile its
+ * block loops over), the block reduces in double (wave shuffles, the waves' partials in wave order), and the block's
+ * total is added in double into the block's slot; gp_metrics sums the slots in slot order. The kernels that count
+ * reward kinds instead (numpy-mode GRID: the windowed and the fused rollout) form (double)count * (double)reward once
+ * per thread per launch, each product exact, and reduce the same way. No float32 partial sum exists anywhere. With N
+ * env-steps of rewards r:
+ *     |return_sum - exact sum| <= N * 2^-52 * sum|r|
+ * (N - 1 additions of relative error 2^-53 each: under half of it). This is the bound the population scores
+ * (gp_controller_scores) already carry per group. Dyadic rewards whose sums fit 53 bits give the exact sum.
+ * The value is deterministic for a given B and launch sequence wherever a block owns its slot (every kernel but the
+ * grid-wide numpy-mode TAXI and CROOMS steps, where more blocks than slots add their totals atomically: their last
+ * bits may differ between runs, inside the bound). Rewards, obs, flags, env state and RNG do not depend on any of this.
+ *
+ * The counters. episodes, length_sum and env_steps are exact integers: 32-bit per thread within one launch, 64-bit
+ * from the wave shuffle on (lanes, waves, slot, host). The per-thread limit of one launch is
+ *     K * envs per thread (4) * tiles per block < 2^32
+ * (CARFLAG's per-thread length sum is 64-bit already); a block's totals may pass 2^32 (a 1,024-env block at
+ * K >= 2^22 with nothing stored). */
 int gp_metrics(gp_env* env, double out[4]);
 
 /* Syncs the handle's device and returns GP_E_DEVICE if any launch since the last seed failed on the

@@ -26,7 +26,7 @@ from oracle.gridworld import ACTIONS_CARDINAL, discrete_states, load_maps
 
 LAYOUT = "4"
 TIME_LIMIT = 40  # above the longest walk to the goal (28 moves; the CPU test asserts it)
-REWARDS = dict(step_reward=-0.25, wall_reward=-0.5, goal_reward=1.0)  # dyadic: float32 sums are exact
+REWARDS = dict(step_reward=-0.25, wall_reward=-0.5, goal_reward=1.0)  # dyadic: the metrics' float64 sums are exact
 GOAL, TRUNC, UNDETERMINED = 1, 2, 3
 
 

@@ -167,7 +167,7 @@ def oracle_rollout(ora, acts, draws):
 def random_model(S, A, O, seed, zero=0.35, n_terminal=1, dyadic=True):
     """(T, Z, R, start, terminal, reset_obs) of a random model: about `zero` of the entries of every law are exactly 0
     (the last entry of a row among them for some rows, so zero tails occur), rewards multiples of 0.25 in [-2, 2]
-    (exact float32 sums), the last `n_terminal` states terminal and never start states."""
+    (exact sums in any order), the last `n_terminal` states terminal and never start states."""
     rng = np.random.default_rng(seed)
 
     def law(*shape):

@@ -138,9 +138,10 @@ def _assert_metrics(env, want):
         assert got[k] == want[k], f"{k}: device {got[k]} oracle {want[k]}"
 
 
-# Dyadic rewards: every partial sum of the kernel's float accumulation (per thread over K steps x 4 envs x tiles, then
-# 64 lanes, then 4 waves) is a multiple of 0.25 below K * 1024 * tiles * 2 < 2^22 and therefore exact in float32, so
-# return_sum compares with == against the float64 sum of the oracle's rewards.
+# Dyadic rewards: every partial sum of the kernel's float64 accumulation (per thread over K steps x 4 envs x tiles, then
+# 64 lanes, then 4 waves, then the slots) is a multiple of 0.25 far below 2^53 / 4 and therefore exact in any order, so
+# return_sum compares with == against the float64 sum of the oracle's rewards. (Rewards that are no short binary
+# fractions, and the bound they are held to: tests/test_metrics_precision_gpu.py.)
 DYADIC = dict(tag_reward=2.0, step_reward=-0.25)
 
 

@@ -17,8 +17,9 @@ pytestmark = pytest.mark.gpu
 
 B0, K0, SEED, TL = 2051, 48, 11, 20
 CASES = {"size6": dict(size=6, min_distance=3.0), "size4": dict(size=4, min_distance=2.0)}
-# Dyadic rewards: every partial sum of the kernel's float accumulation is a multiple of 0.25 far below 2^24 and
-# therefore exact in float32, so return_sum compares with == (tests/test_anttag_gpu.py states the bound).
+# Dyadic rewards: every partial sum of the kernel's float64 accumulation is a multiple of 0.25 far below 2^53 / 4 and
+# therefore exact, so return_sum compares with == (tests/test_anttag_gpu.py; other rewards:
+# tests/test_metrics_precision_gpu.py).
 DYADIC = dict(tag_reward=2.0, step_reward=-0.25)
 
 

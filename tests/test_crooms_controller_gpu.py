@@ -30,7 +30,7 @@ from oracle.philox import philox_key
 pytestmark = pytest.mark.gpu
 
 B, K, SEED, TL = 1027, 48, 11, 20
-DYADIC = dict(step_reward=-0.25, wall_reward=-0.5, goal_reward=1.0)  # float32 sums are exact in any order
+DYADIC = dict(step_reward=-0.25, wall_reward=-0.5, goal_reward=1.0)  # float64 sums are exact in any order
 OUTPUTS = ("obs", "actions", "nodes", "rew", "term", "trunc")
 CONFIGS = {
     "card_hansen": dict(action_type="cardinal", obs_type="hansen"),  # the fixed default goal

@@ -161,13 +161,19 @@ def test_philox_specialised_kernel_equals_generic(B, K, gpu_device):
     a.reset(seed=21)
     b.reset(seed=21)
     acts = torch.rand((K, B, 2), device=gpu_device) * 2 - 1
-    for x, y in zip(a.rollout(acts), b.rollout(acts)):
+    out = a.rollout(acts)
+    for x, y in zip(out, b.rollout(acts)):
         assert torch.equal(x, y)
     for x, y in zip(a.get_state(), b.get_state()):
         assert torch.equal(x, y)
     ma, mb = a.metrics(), b.metrics()
     assert {k: v for k, v in ma.items() if k != "return_sum"} == {k: v for k, v in mb.items() if k != "return_sum"}
-    assert ma["return_sum"] == pytest.approx(mb["return_sum"], rel=1e-6)
+    # the law of gp_metrics: each float64 sum is within (N - 1) * 2^-53 * sum|r| of the exact one, so the two differ by
+    # less than N * 2^-52 * sum|r| (and the exact one is the plane's own sum)
+    r = out[1].double()
+    bound = r.numel() * 2.0 ** -52 * float(r.abs().sum())
+    assert abs(ma["return_sum"] - mb["return_sum"]) <= bound
+    assert abs(ma["return_sum"] - float(r.sum())) <= bound
 
 
 def test_philox_action_noise_law(gpu_device):

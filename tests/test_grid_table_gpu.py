@@ -8,9 +8,9 @@ where they can differ, so every (agent cell, intended action) row of the `grid_t
 own cell; elapsed 0, time_limit - 1 and time_limit) goes through each of them in ONE launch from the recorded pre-step
 stream state: the four outputs, get_state(), the final PCG64 state and the four metrics, all compared with ==.
 
-return_sum: the rewards are 2, -1 and -0.25, a block sums at most 2048 x 2 envs of them in float32 and the host adds
-the blocks in float64: every partial sum is a multiple of 0.25 below 2^24 / 4, hence exact, and equal to the float64
-sum of the fixture's rewards.
+return_sum: the rewards are 2, -1 and -0.25 and the device sums them (or counts times rewards) in float64 from the
+thread on: every partial sum is a multiple of 0.25 far below 2^53 / 4, hence exact in any order, and equal to the
+float64 sum of the fixture's rewards. (Rewards that are no short binary fractions: tests/test_metrics_precision_gpu.py.)
 """
 import contextlib
 import functools

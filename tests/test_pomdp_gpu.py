@@ -19,9 +19,10 @@ from pomdp_oracle import TAG, TIGER, TOP, PomdpOracle, Spec, oracle_rollout, ran
 
 pytestmark = pytest.mark.gpu
 
-# Rewards are multiples of 0.25 (Tiger's: integers up to 100): every partial sum of the kernel's float32 accumulation
-# (per thread over K steps x 4 envs x tiles, then 64 lanes, then 4 waves) is a multiple of 0.25 below 2^22 and therefore
-# exact, so return_sum compares with == against the float64 sum of the oracle's rewards.
+# Rewards are multiples of 0.25 (Tiger's: integers up to 100): every partial sum of the kernel's float64 accumulation
+# (per thread over K steps x 4 envs x tiles, then 64 lanes, then 4 waves, then the slots) is a multiple of 0.25 far
+# below 2^53 / 4 and therefore exact in any order, so return_sum compares with == against the float64 sum of the
+# oracle's rewards. (Rewards that are no short binary fractions: tests/test_metrics_precision_gpu.py.)
 MODELS = {"tiger": None, "m5": (5, 2, 3), "m37": (37, 3, 21), "m300": (300, 2, 70)}
 # name -> the model blob is staged in LDS under the default budget (32 KB): m37's is 48,608 B, m300's 1.5 MB
 DEFAULT_LDS = {"tiger": 1, "m5": 1, "m37": 0, "m300": 0}

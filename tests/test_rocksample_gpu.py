@@ -15,9 +15,10 @@ from rocksample_oracle import BAD, GOOD, RockSampleOracle, Spec, oracle_rollout
 
 pytestmark = pytest.mark.gpu
 
-# Dyadic rewards: every partial sum of the kernel's float32 accumulation (per thread over K steps x 4 envs x tiles,
-# then 64 lanes, then 4 waves) is a multiple of 0.25 far below 2^22 and therefore exact, so return_sum compares with
-# == against the float64 sum of the oracle's rewards.
+# Dyadic rewards: every partial sum of the kernel's float64 accumulation (per thread over K steps x 4 envs x tiles,
+# then 64 lanes, then 4 waves, then the slots) is a multiple of 0.25 far below 2^53 / 4 and therefore exact in any
+# order, so return_sum compares with == against the float64 sum of the oracle's rewards. (Rewards that are no short
+# binary fractions: tests/test_metrics_precision_gpu.py.)
 DYADIC = dict(exit_reward=4.0, good_reward=2.0, bad_reward=-2.0, empty_reward=-1.0, check_reward=-0.25,
               step_reward=-0.5, wall_reward=-0.75)
 ROCKS_232 = ((0, 1), (1, 2))

@@ -13,7 +13,7 @@ tables by default; larger tables, and every table on the 8 x 8 map, are read fro
 B = 2,051 envs = three 1,024-env tiles, the last one holding 3 live envs in one thread's quad. K = 48 steps under
 time_limit = 20: an episode lasts at most 21 steps, so every env ends at least two, and an env that never terminates
 ends exactly two by truncation. Everything is compared with ==; the rewards are dyadic (multiples of 0.25, |r| <= 2),
-so the float32 sums of the metrics are exact (at most 3 x 1,024 x 48 env-steps per block and launch, below 2^21).
+so the float64 sums of the metrics are exact in any order (other rewards: tests/test_metrics_precision_gpu.py).
 """
 import contextlib
 import functools

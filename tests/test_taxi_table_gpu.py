@@ -15,11 +15,10 @@ table trans[s * 6 + a] and obs_of[s]. Random walks hardly reach a goal move, so 
   (e) blocks loop over several 1,024-env tiles;
   (f) the 4-bit dropoff count saturates instead of spilling into elapsed.
 
-Everything is compared with ==. The metrics' return_sum is a float32 sum per block and launch: with the dyadic
-rewards used here (multiples of 0.25, |r| <= 2) every partial sum is a multiple of 0.25 below 2^22, hence exact, while
-    max|reward| x env-steps per block per launch < 2^22,  i.e. fewer than 2^21 env-steps per block per launch.
-The largest here: the one-workgroup numpy kernel sums its whole batch in one block (30,000 x 1 and 4,099 x 48
-env-steps per launch); a block of the persistent rollout kernel sums its tiles (at most 3 x 1,024 x 48).
+Everything is compared with ==. The metrics' return_sum is a float64 sum from the thread on: with the dyadic
+rewards used here (multiples of 0.25, |r| <= 2) every partial sum is a multiple of 0.25 far below 2^53 / 4, hence exact
+in any order (the one-workgroup numpy kernel sums its whole batch in one block, the grid-wide one adds its blocks'
+totals atomically). Rewards that are no short binary fractions: tests/test_metrics_precision_gpu.py.
 """
 import contextlib
 import functools
