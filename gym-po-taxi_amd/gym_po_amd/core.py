@@ -587,6 +587,9 @@ class NativeVecEnv:
         check(lib().gp_get_state(self._handle, *ptrs, self._stream()), "gp_get_state")
 
     def _set_state_raw(self, bufs):
+        """gp_set_state from device tensors (the dtypes of get_state(), None leaves a field alone): asynchronous on the
+        current stream. The envs' public set_state(...) wrappers accept host arrays, so they upload, call this and then
+        synchronise the current stream before they return (Streams)."""
         ptrs = [ctypes.c_void_p(b.data_ptr()) if b is not None else None for b in bufs]
         ptrs += [None] * (4 - len(ptrs))
         check(lib().gp_set_state(self._handle, *ptrs, self._stream()), "gp_set_state")

@@ -291,7 +291,9 @@ int gp_obs_info(const gp_env* env, int* dtype, int* width);
 int64_t gp_num_envs(const gp_env* env);
 
 /* numpy-compatible seeding: SeedSequence(entropy, spawn_key) -> PCG64 (and the Philox key).
- * entropy = little-endian uint32 words of a non-negative integer (numpy's convention). */
+ * entropy = little-endian uint32 words of a non-negative integer (numpy's convention).
+ * Synchronous: both wait for the device (they clear the device error word, which queued launches may still write),
+ * so a seed given after queued work takes effect after that work. */
 int gp_seed_words(gp_env* env, const uint32_t* entropy, int n_entropy, const uint32_t* spawn_key, int n_spawn);
 int gp_seed(gp_env* env, uint64_t seed);
 /* raw PCG64 state: {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}. get syncs. */
