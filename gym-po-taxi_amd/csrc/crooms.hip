@@ -2792,6 +2792,7 @@ struct CRoomsBackend : EnvBackend {
     has_reset = true;
     return GP_OK;
   }
+  bool in_step_loop = false;  // inside the K single steps of a replay rollout (the bases were checked by the call)
   int rollout(int K, const void* act, void* obs, float* rew, uint8_t* term, uint8_t* trunc, hipStream_t s) override {
     if (!has_reset) {
       gp_set_error("step() before reset()");
@@ -2811,12 +2812,19 @@ struct CRoomsBackend : EnvBackend {
         gp_set_error("crooms replay step needs wall noise (f1) and reset indices (i0/i1)");
         return GP_E_STATE;
       }
-      if (K > 1) return EnvBackend::rollout(K, act, obs, rew, term, trunc, s);
     }
+    // The bases are checked once per call. The K single steps of a replay rollout run on the planes of their own
+    // step, which need not keep that alignment (odd B), exactly as the planes k > 0 of a K-step launch need not.
     auto al = [](const void* x, uintptr_t m) { return ((uintptr_t)x & (m - 1)) == 0; };
-    if (!al(act, d.action_kind == 0 ? (d.action_f64 ? 16 : 8) : 4) || !al(obs, 16) || !al(rew, 4)) {
+    if (!in_step_loop && (!al(act, d.action_kind == 0 ? (d.action_f64 ? 16 : 8) : 4) || !al(obs, 16) || !al(rew, 4))) {
       gp_set_error("crooms: misaligned action / obs / reward buffer");
       return GP_E_INVALID;
+    }
+    if (rep && K > 1) {
+      in_step_loop = true;
+      const int e = EnvBackend::rollout(K, act, obs, rew, term, trunc, s);
+      in_step_loop = false;
+      return e;
     }
     if (rng_mode == GP_RNG_NUMPY) {
       timer.begin(s);

@@ -2964,6 +2964,7 @@ struct GridBackend : EnvBackend {
   size_t wg_lds = 0;
   int at_launches = 0, at_steps = 0;  // the last gp_autotune's scratch launches (both kernels) and their length
   float at_ms[2] = {0.f, 0.f};        // its mean ms per launch: windowed, fused
+  int64_t np_launches[3] = {0, 0, 0};  // numpy-mode launches since gp_create: windowed, fused, step kernels
   WgParams wg{};
   std::vector<char> wg_img;        // LDS image of its tables (the PCG jump parts rebuilt on every seed)
   DevBuf b_wgp, b_wlimg, b_wjlane, b_wjrej, b_wjblk, b_wslots, b_wjfirst;
@@ -3004,6 +3005,10 @@ struct GridBackend : EnvBackend {
     else if (!strcmp(key, "wgrid_halo")) *v = wg_H;
     else if (!strcmp(key, "wgrid_kmax")) *v = wg_kmax;
     else if (!strcmp(key, "wgrid_lds")) *v = (int64_t)wg_lds;  // dynamic LDS bytes of one launch
+    // numpy mode: which kernel the launches since gp_create took (the step kernels count one per step)
+    else if (!strcmp(key, "launches_windowed")) *v = np_launches[0];
+    else if (!strcmp(key, "launches_fused")) *v = np_launches[1];
+    else if (!strcmp(key, "launches_step")) *v = np_launches[2];
     // the last autotune: launches it made (both kernels, incl. one warm launch each), their length, and the mean
     // time per launch of each kernel in ns
     else if (!strcmp(key, "autotune_launches")) *v = at_launches;
@@ -3098,6 +3103,7 @@ struct GridBackend : EnvBackend {
   }
   int launch_wgrid(int K, const void* act, void* obs, float* rew, uint8_t* term, uint8_t* trunc, hipStream_t s) {
     const WgArgs a{b_wgp.as<WgParams>(), K, (const int32_t*)act, (int32_t*)obs, rew, term, trunc};
+    ++np_launches[0];
     timer.begin(s);
     const int e = wgrid_launch(a, wg_NS, d.nact, wg_G, wg_lds, s);
     timer.end(s);
@@ -3147,6 +3153,7 @@ struct GridBackend : EnvBackend {
   }
   template <int OK>
   int launch_fused(int K, const void* act, void* obs, float* rew, uint8_t* term, uint8_t* trunc, hipStream_t s) {
+    ++np_launches[1];
     timer.begin(s);
     switch (fused_qpt) {
       case 1: launch_fused_q<OK, 1>(K, act, obs, rew, term, trunc, s); break;
@@ -3513,6 +3520,7 @@ int GridBackend::step(const void* act, void* obs, float* rew, uint8_t* term, uin
     if (rng_mode == GP_RNG_NUMPY) {
       if (wgrid_pick(1, act, obs, rew, term, trunc)) return launch_wgrid(1, act, obs, rew, term, trunc, s);
       if (fused_ok(act, obs, rew, term, trunc)) return launch_fused<OK>(1, act, obs, rew, term, trunc, s);
+      ++np_launches[2];
       timer.begin(s);
       hipLaunchKernelGGL(grid_step_numpy<OK>, dim3(d.nblk), dim3(TPB), 0, s, d, (const int32_t*)act, obs, rew, term,
                          trunc);

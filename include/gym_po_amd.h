@@ -300,7 +300,8 @@ int gp_seed(gp_env* env, uint64_t seed);
 int gp_set_rng_state(gp_env* env, const uint64_t st[6]);
 int gp_get_rng_state(gp_env* env, uint64_t st[6]);
 
-/* Reset every env (reset()), writing the initial observation to `obs` (device). */
+/* Reset every env (reset()), writing the initial observation to `obs` (device). `obs` may sit at any address that is
+ * aligned to its element type; exactly the B observations are written. */
 int gp_reset(gp_env* env, void* obs, void* stream);
 
 /* One batched step with same-step autoreset. actions: int32 [B] (discrete), float [B,2]
@@ -311,7 +312,22 @@ int gp_step(gp_env* env, const void* actions, void* obs, float* rew, uint8_t* te
 
 /* K consecutive steps. actions [K,B(,2)], outputs [K,B,...]. Philox mode, and numpy mode on GRID
  * (persistent kernel with a per-step grid exchange; 16-B aligned buffers, B % 4 == 0), fuse the K
- * steps in one launch with the state in registers; other cases issue K step launches. */
+ * steps in one launch with the state in registers; other cases issue K step launches.
+ *
+ * Caller buffers (gp_step, gp_rollout, gp_plan_*). Every buffer may sit at any address aligned to its element type (4 B
+ * for int32 / float planes, 8 B for float64, any byte for uint8 planes), and B need not be a multiple of anything: the
+ * kernels choose their store width per buffer and per step, and write exactly the documented bytes of the outputs and
+ * never an input. Off 16 B a plane takes narrower stores (slower, same values). Exceptions:
+ *   GRID in GP_RNG_NUMPY never refuses: when a buffer is off the boundaries above (windowed kernel: outputs on 16 B;
+ *     fused kernel: actions, obs and rew on 16 B, term / trunc on 4 B, B % 4 == 0) the launch falls back, from the
+ *     windowed to the fused kernel and from there to K single steps, each of which chooses again from the addresses of
+ *     its own planes (one step needs no B % 4 == 0) between those kernels and the step kernels, with identical results.
+ *     gp_query "launches_windowed" / "launches_fused" / "launches_step" count which one ran.
+ *   CROOMS refuses (GP_E_INVALID, "crooms: misaligned action / obs / reward buffer") an obs base off 16 B and a
+ *     continuous action base off 16 B (float64 [B,2]) or 8 B (float32 [B,2]); the planes of later steps need not keep
+ *     that alignment, and rew / term / trunc go anywhere.
+ *   ANTTAG with the vector obs refuses (GP_E_INVALID, "anttag: obs buffer must be 16-B aligned") an obs base off 16 B.
+ * A refused call writes nothing and advances nothing (state, step index, metrics). */
 int gp_rollout(gp_env* env, int K, const void* actions, void* obs, float* rew, uint8_t* term, uint8_t* trunc,
                void* stream);
 /* A prepared gp_rollout (the agent loop's allocation-free hot path, bench.py's timed call): the arguments are
@@ -388,7 +404,10 @@ void gp_plan_destroy(gp_plan* plan);
  * gp_rollout_controller runs K steps in one launch. obs [K,B] int32, rew [K,B] float, term / trunc [K,B] uint8 as
  * gp_rollout; actions int32 [K,B]: the actions taken; nodes uint8 [K,B]: the node each action was chosen in. Every
  * output pointer may be NULL (not stored); with all of them NULL the call is a pure policy evaluation, read through
- * gp_metrics. GP_E_STATE before gp_reset or without a controller.
+ * gp_metrics. GP_E_STATE before gp_reset or without a controller. The planes may sit at any element-aligned address
+ * (as gp_rollout's), except CROOMS, whose kernel stores pairs of envs: obs, actions and rew off 8 B, or nodes, term and
+ * trunc off 2 B, are refused (GP_E_INVALID, "crooms: misaligned obs / action / reward (8 B) or node / flag (2 B)
+ * buffer"; NULL planes are not checked); the refused call writes and advances nothing.
  * gp_controller_nodes: get (device uint8 [B], may be NULL) receives the nodes, then set (device uint8 [B], may be
  * NULL) replaces them, both asynchronously on `stream`. A node >= n_nodes is clamped and flagged by the next
  * closed-loop launch. */
@@ -658,8 +677,10 @@ int gp_autotune(gp_env* env, int K, int reps, int* chosen);
  * "controller_nodes" and "controller_lds" answer for one controller's table. Every kind with closed-loop rollouts
  * also: "controller_n_obs" and "controller_actions" (n_obs of the installed table and the env's A: the shape
  * gp_controller_stats uses; GP_E_STATE without a controller), "stats_lds" (the path of the handle's last
- * gp_controller_stats launch: 1 LDS histogram, 0 global atomics, -1 none yet). Unknown keys return
- * GP_E_INVALID. */
+ * gp_controller_stats launch: 1 LDS histogram, 0 global atomics, -1 none yet). GRID also: "launches_windowed",
+ * "launches_fused", "launches_step" (GP_RNG_NUMPY: the launches since gp_create that took the windowed kernel, the
+ * fused kernel and the step kernels, the last counting one per step; gp_autotune's scratch launches included). Unknown
+ * keys return GP_E_INVALID. */
 int gp_query(const gp_env* env, const char* key, int64_t* value);
 /* ---- the normal sampler of rng_mode=philox (C-ROOMS noise), diagnostics ----
  * Replaces numpy's Generator.standard_normal (numpy/random/src/distributions/distributions.c,
