@@ -570,6 +570,13 @@ int gp_belief_backup(gp_env* env, int n_points, const float* points, int n_vecto
                                 (hipStream_t)stream);
 }
 
+int gp_belief_expand(gp_env* env, int n_points, const float* points, int n_ref, const float* ref, float* succ_out,
+                     float* dist_out, int32_t* act_out, int32_t* obs_out, float* mass_out, void* stream) {
+  GP_REQUIRE_ENV();
+  return env->be->belief_expand(n_points, points, n_ref, ref, succ_out, dist_out, act_out, obs_out, mass_out,
+                                (hipStream_t)stream);
+}
+
 int gp_get_state(gp_env* env, void* a, void* b, void* c, void* d, void* stream) {
   GP_REQUIRE_ENV();
   return env->be->get_state(a, b, c, d, (hipStream_t)stream);

@@ -180,6 +180,11 @@ struct EnvBackend {
                             int32_t* act_out, float* value_out, hipStream_t s) {
     return no_belief();
   }
+  // Belief-set expansion (gp_belief_expand; pomdp_expand.hip): POMDP only.
+  virtual int belief_expand(int P, const float* points, int Q, const float* ref, float* succ_out, float* dist_out,
+                            int32_t* act_out, int32_t* obs_out, float* mass_out, hipStream_t s) {
+    return no_belief();
+  }
   int stats_path = -1;  // the last gp_controller_stats launch: 1 = LDS histogram, 0 = global atomics (gp_query "stats_lds")
   virtual int valid_cells(int which, int32_t* out, int cap) const { return 0; }
   virtual int metrics(double out[4]) = 0;  // (the sum of the kind's MetricSlots: gp_common.h sum_metric_slots)

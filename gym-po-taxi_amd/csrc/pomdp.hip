@@ -43,6 +43,7 @@
 #include "gp_ctrl.h"
 #include "gp_internal.h"
 #include "pomdp_backup.h"
+#include "pomdp_expand.h"
 
 namespace {
 
@@ -592,12 +593,14 @@ struct PomdpBackend : EnvBackend {
   int grid_bel = 1, grid_filt = 1;
   DevBuf b_bel[2], b_prior, b_cp, b_ent, b_alpha, b_vact;
   PbHost pb;  // the point-based backup's tables, vectors and scratch (gp_belief_backup; pomdp_backup.hip)
+  PxHost px;  // the expansion's scratch beside it (gp_belief_expand; pomdp_expand.hip)
 
   int build(const gp_pomdp_config* cfg);
   int belief_enable(const float* prior) override;
   int belief_disable() override {
     belief_on = belief_oc = false;
     pb.release();
+    px.release();
     for (DevBuf* b : {&b_bel[0], &b_bel[1], &b_prior, &b_cp, &b_ent}) (void)b->alloc(0);
     bf.bel[0] = bf.bel[1] = nullptr;
     bf.prior = nullptr;
@@ -652,16 +655,25 @@ struct PomdpBackend : EnvBackend {
   }
   int set_belief_policy(int n_vec, const float* alpha, const int32_t* vec_action) override;
   // gp_belief_backup: reads the model and the filter's float laws, writes only its outputs
-  int belief_backup(int P, const float* points, int N, const float* alpha, float gamma, float* alpha_out,
-                    int32_t* act_out, float* value_out, hipStream_t s) override {
-    if (int e = belief_ready("gp_belief_backup")) return e;
+  PbModel backup_model() const {
     PbModel m;
     m.S = d.S, m.A = d.A, m.O = d.O, m.Sp = d.Sp, m.Op = d.Op;
     m.blob = d.blob;
     m.off_obs = d.off_obs, m.off_rew = d.off_rew, m.off_term = d.off_term;
     m.colptr = bf.colptr;
     m.ent = bf.ent;
-    return pb.backup(m, P, points, N, alpha, gamma, alpha_out, act_out, value_out, s);
+    return m;
+  }
+  int belief_backup(int P, const float* points, int N, const float* alpha, float gamma, float* alpha_out,
+                    int32_t* act_out, float* value_out, hipStream_t s) override {
+    if (int e = belief_ready("gp_belief_backup")) return e;
+    return pb.backup(backup_model(), P, points, N, alpha, gamma, alpha_out, act_out, value_out, s);
+  }
+  // gp_belief_expand: as the backup, reads the model and writes only its outputs
+  int belief_expand(int P, const float* points, int Q, const float* ref, float* succ_out, float* dist_out,
+                    int32_t* act_out, int32_t* obs_out, float* mass_out, hipStream_t s) override {
+    if (int e = belief_ready("gp_belief_expand")) return e;
+    return px.expand(pb, backup_model(), P, points, Q, ref, succ_out, dist_out, act_out, obs_out, mass_out, s);
   }
   int rollout_belief(int K, void* obs, int32_t* act, int32_t* vec, float* value, float* rew, uint8_t* term,
                      uint8_t* trunc, hipStream_t s) override {
@@ -732,6 +744,7 @@ struct PomdpBackend : EnvBackend {
     else if (!strcmp(key, "belief_vectors")) *v = bf.N;             // vectors of the installed policy (0 = none)
     else if (!strcmp(key, "backup_scratch_bytes")) *v = (int64_t)pb.scratch_bytes();  // gp_belief_backup's scratch
     else if (!strcmp(key, "backup_tables")) *v = pb.built;          // its compressed tables are built
+    else if (!strcmp(key, "expand_scratch_bytes")) *v = (int64_t)(pb.b_acc.n + px.own_bytes());  // gp_belief_expand's (acc is the backup's)
     else return EnvBackend::query(key, v);
     return GP_OK;
   }

@@ -30,4 +30,7 @@ struct PbHost {
   int build(const PbModel& m);
   int backup(const PbModel& m, int P, const float* points, int N, const float* alpha, float gamma, float* alpha_out,
              int32_t* act_out, float* value_out, hipStream_t s);
+  // Step 1 alone, for the expansion (pomdp_expand.hip): builds the tables if need be, grows b_acc to P points and
+  // launches pb_acc on `s`. acc [P][A][S] is then b_acc.
+  int acc_points(const PbModel& m, int P, const float* points, hipStream_t s);
 };

@@ -224,6 +224,30 @@ int PbHost::build(const PbModel& m) {
   return GP_OK;
 }
 
+// The caller has validated P (>= 1) and the scratch size.
+int PbHost::acc_points(const PbModel& m, int P, const float* points, hipStream_t s) {
+  int e;
+  if (!built && (e = build(m))) return e;
+  const size_t need_acc = (size_t)P * m.A * m.S * sizeof(float);
+  if (b_acc.n < need_acc) {  // (an earlier call queued on any stream may still use it: freed once the device is idle)
+    GP_HIP_CHECK(hipDeviceSynchronize());
+    if ((e = b_acc.alloc(need_acc))) return e;
+    GP_HIP_CHECK(hipDeviceSynchronize());
+  }
+  PbDev d{};
+  d.S = m.S;
+  d.A = m.A;
+  d.O = m.O;
+  d.P = P;
+  d.colptr = m.colptr;
+  d.ent = m.ent;
+  d.points = points;
+  d.acc = b_acc.as<float>();
+  hipLaunchKernelGGL(pb_acc, dim3((unsigned)(((size_t)P * m.A * m.S + TPB - 1) / TPB)), dim3(TPB), 0, s, d);
+  GP_HIP_CHECK(hipGetLastError());
+  return GP_OK;
+}
+
 // Validates, copies the vectors to the device (after the stream's earlier work: an earlier call may still read the
 // handle's copy), grows the scratch if this call needs more, and launches the four kernels on `s`.
 int PbHost::backup(const PbModel& m, int P, const float* points, int N, const float* alpha, float gamma,

@@ -16,8 +16,10 @@ from .envs import __all__ as _envs_all  # noqa: E402
 
 from .controller import controller_thresholds, population_thresholds  # noqa: E402
 from .pomdp_file import parse_pomdp  # noqa: E402
-from .belief import collect_beliefs, float_laws, parse_alpha, pbvi, qmdp_vectors  # noqa: E402
+from .belief import (collect_beliefs, expand_points, float_laws, is_closed, parse_alpha, pbvi,  # noqa: E402
+                     pbvi_expanding, qmdp_vectors, reset_points)
 
 __all__ = list(_envs_all) + ["controller_thresholds", "population_thresholds", "parse_pomdp", "float_laws",
-                             "parse_alpha", "qmdp_vectors", "collect_beliefs", "pbvi"]
+                             "parse_alpha", "qmdp_vectors", "collect_beliefs", "pbvi", "reset_points", "expand_points",
+                             "is_closed", "pbvi_expanding"]
 __version__ = "0.1.0"

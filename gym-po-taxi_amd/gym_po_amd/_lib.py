@@ -127,6 +127,7 @@ SIGNATURES = {
     "gp_set_belief_policy": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     "gp_rollout_belief": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_belief_backup": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "gp_belief_expand": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_get_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gp_set_replay": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

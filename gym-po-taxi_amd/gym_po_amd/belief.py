@@ -1,8 +1,11 @@
 """Belief-space helpers of the tabular POMDP env: the float32 laws the on-device Bayes filter multiplies (DESIGN.md
 §6r), QMDP alpha-vectors, a reader of `pomdp-solve`'s `.alpha` files (pure numpy), and the drivers of the on-device
 point-based backup: `collect_beliefs` steps an env and gathers its beliefs, `pbvi` iterates
-`TabularPOMDPEnv.point_backup` (or any backup given) over a fixed point set. `TabularPOMDPEnv.set_belief_policy` takes
-the vectors these return.
+`TabularPOMDPEnv.point_backup` (or any backup given) over a fixed point set; and the drivers of the on-device
+belief-set expansion: `reset_points` are the beliefs an episode starts with, `expand_points` grows a
+set by every point's farthest successor (`TabularPOMDPEnv.expand_beliefs`, or any expansion given), `is_closed` says
+whether a set holds all its successors, and `pbvi_expanding` alternates `pbvi` and `expand_points` from the reset
+beliefs alone. `TabularPOMDPEnv.set_belief_policy` takes the vectors these return.
 """
 import numpy as np
 
@@ -139,6 +142,81 @@ def pbvi(env, points, gamma, sweeps, backup=None):
         alpha, actions = new[first], _host(out["actions"]).astype(np.int64)[first]
         values.append(_host(out["value"]).astype(np.float32))
     return alpha, actions, np.stack(values)
+
+
+def reset_points(env, prior=None):
+    """The beliefs an episode can start with: for every reset obs o the filter's ended rule on the prior,
+    u(s) = fl(prior[s] Rf[s][o]), n = sum_s u(s) (sequential, ascending, from +0), b(s) = fl(u(s) / n), in float32 from
+    `float_laws(env)` (pure numpy). `prior` None: the env's start law, enable_belief()'s default; an env enabled with
+    `enable_belief(prior)` takes the same `prior` here (normalised as there, by `normalise_belief`), else these are not
+    the beliefs its filter resets to. An obs with !(n > 0) or n not finite never opens an episode and is left out.
+    Returns the `distinct_rows` of the rest, float32 [P, S]: the seed set of `pbvi_expanding` (which uses the start
+    law: pass `points=reset_points(env, prior)` for another), and the successors through an episode end that
+    `expand_beliefs` leaves out."""
+    lw = float_laws(env)
+    if prior is not None:
+        prior = normalise_belief(prior)
+        if prior.shape != lw["prior"].shape:
+            raise ValueError(f"prior must be [S] = [{lw['prior'].shape[0]}], got shape {prior.shape}")
+        lw["prior"] = prior
+    u = (lw["prior"][None, :] * lw["Rf"].T).astype(np.float32)  # [O, S]
+    n = np.zeros(u.shape[0], dtype=np.float32)
+    for s in range(u.shape[1]):
+        n = (n + u[:, s]).astype(np.float32)
+    live = (n > 0) & np.isfinite(n)
+    return distinct_rows((u[live] / n[live, None]).astype(np.float32))
+
+
+def _expansion(env, points, expand):
+    pts = points if hasattr(points, "detach") else np.ascontiguousarray(points, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != int(env.n_states) or pts.shape[0] < 1:
+        raise ValueError(f"points must be [P, S] = [P, {int(env.n_states)}] with P >= 1, got {tuple(pts.shape)}")
+    out = (env.expand_beliefs if expand is None else expand)(pts)
+    return pts, np.ascontiguousarray(_host(out["succ"]), dtype=np.float32), _host(out["dist"]).astype(np.float32)
+
+
+def expand_points(env, points, expand=None):
+    """One expansion of the belief set `points` [P, S] (Pineau, Gordon & Thrun 2003): every point proposes its
+    farthest successor (`expand(points)` -> a dict with succ [P, S] and dist [P]; None: `env.expand_beliefs`, measured
+    against the points themselves), the successors with dist > 0 are kept, and the `distinct_rows` of the points and
+    the kept successors are returned, float32 (numpy): the set at most doubles."""
+    pts, succ, dist = _expansion(env, points, expand)
+    return distinct_rows(np.concatenate((np.ascontiguousarray(_host(pts), dtype=np.float32), succ[dist > 0])))
+
+
+def is_closed(env, points, expand=None):
+    """True iff every successor of positive probability of every point of `points` [P, S] that does not pass through an
+    episode end is itself a point, bit for bit: one expansion in which every dist is 0. With `reset_points` among the
+    points the set is then closed under the filter, which is where point-based value iteration improves monotonically
+    (DESIGN.md §6s)."""
+    return bool(np.all(_expansion(env, points, expand)[2] == 0))
+
+
+def pbvi_expanding(env, gamma, rounds, sweeps, points=None, backup=None, expand=None):
+    """Point-based value iteration with its belief-set expansion: `rounds` rounds of `pbvi(env, points, gamma, sweeps,
+    backup)` (each from pbvi's own start vector, not from the round before's vectors: pbvi keeps its signature, at the
+    price of rounds x sweeps backups), with one `expand_points` between two rounds. `points` None: start from
+    `reset_points(env)`. Stops early, after the round on it, once an expansion adds no point (the set is closed).
+    Returns (alpha, actions, points, values_per_round): the vectors and actions of the last round (what
+    `set_belief_policy` takes), the final point set float32 [P, S], and per round the float32 [sweeps, P_round] values
+    of pbvi."""
+    rounds = int(rounds)
+    if rounds < 1:
+        raise ValueError(f"pbvi_expanding: rounds must be >= 1, got {rounds}")
+    pts = reset_points(env) if points is None else distinct_rows(points)
+    if pts.shape[0] < 1:
+        raise ValueError("pbvi_expanding: no point to start from")
+    values = []
+    for r in range(rounds):
+        alpha, actions, v = pbvi(env, pts, gamma, sweeps, backup)
+        values.append(v)
+        if r + 1 == rounds:
+            break
+        grown = expand_points(env, pts, expand)
+        if grown.shape[0] == pts.shape[0]:
+            break
+        pts = grown
+    return alpha, actions, pts, values
 
 
 def parse_alpha(text, S):

@@ -373,6 +373,61 @@ class TabularPOMDPEnv(NativeVecEnv):
         # work queued behind them on that stream)
         return bufs
 
+    # ------------------------------------------------------------------ belief-set expansion ----
+    _EXPAND_OUTPUTS = ("succ", "dist", "actions", "obs", "mass")
+
+    def expand_beliefs(self, points, ref=None, out=None):
+        """One belief-set expansion (csrc/pomdp_expand.hip; the rule is stated in
+        include/gym_po_amd.h): for every belief point the successor b' under the filter, over every action and obs of
+        positive probability, whose L1 distance to the nearest row of `ref` is largest (the first such, actions then
+        obs ascending). `points` [P, S] and `ref` [Q, S] with Q >= 1 (None: the points themselves) are validated as
+        point_backup validates points (finite, >= 0, a positive sum per row) and not normalised. Returns a dict of succ
+        float32 [P, S], dist float32 [P], actions int32 [P], obs int32 [P] and mass float32 [P] (the probability of
+        that obs) on the device; `out` may hold contiguous tensors of these shapes to write into. A point without a
+        successor of positive probability gives actions = obs = -1, dist = mass = 0 and a row of zeros. dist == 0
+        everywhere says that the set is closed under the filter's successors. Needs enable_belief(); reads the model
+        only; asynchronous on the current stream."""
+        torch = _torch()
+        fn = self._ctrl_fn("gp_belief_expand")
+        S = self.n_states
+
+        def rows(name, n, x):
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+            if t.dim() != 2 or t.shape[1] != S:
+                raise ValueError(f"expand_beliefs: {name} must be [{n}, S] = [{n}, {S}], got {tuple(t.shape)}")
+            if t.shape[0] and (not bool((torch.isfinite(t) & (t >= 0)).all()) or not bool((t.sum(-1) > 0).all())):
+                raise ValueError(f"expand_beliefs: {name} must be finite and >= 0, and every row needs a positive sum")
+            return t
+        t = rows("points", "P", points)
+        q = None if ref is None else rows("ref", "Q", ref)
+        if q is not None and q.shape[0] < 1:
+            raise ValueError("expand_beliefs: ref must have at least one row (None: the points themselves)")
+        P = t.shape[0]
+        want = {"succ": ((P, S), torch.float32), "dist": ((P,), torch.float32), "actions": ((P,), torch.int32),
+                "obs": ((P,), torch.int32), "mass": ((P,), torch.float32)}
+        if out is not None and not isinstance(out, dict):
+            raise ValueError("out must be a dict of tensors by output name")
+        bufs = {}
+        for name in self._EXPAND_OUTPUTS:
+            shape, dt = want[name]
+            b = None if out is None else out.get(name)
+            if b is None:
+                b = torch.empty(shape, dtype=dt, device=self.device)
+            elif not isinstance(b, torch.Tensor):
+                raise ValueError(f"out {name}: expected a torch tensor")
+            elif tuple(b.shape) != shape or b.dtype != dt or b.device != self.device or not b.is_contiguous():
+                raise ValueError(f"out {name}: need a contiguous {dt} tensor of shape {shape} on {self.device}, got "
+                                 f"{b.dtype} {tuple(b.shape)} on {b.device} (contiguous={b.is_contiguous()})")
+            bufs[name] = b
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
+        _lib.check(fn(self._handle, P, ptr(t), 0 if q is None else q.shape[0], None if q is None else ptr(q),
+                      ptr(bufs["succ"]), ptr(bufs["dist"]), ptr(bufs["actions"]), ptr(bufs["obs"]), ptr(bufs["mass"]),
+                      self._stream()), "gp_belief_expand")
+        # (the launches read `t` and `q` on the current stream: the caching allocator hands their memory out again
+        # only to work queued behind them on that stream)
+        return bufs
+
 
 def heaven_hell_pomdp(env):
     """(T, Z, R, start, terminal, reset_obs) of a `HeavenHellGridEnv`: the same task as tables. S = 2 H W with state =

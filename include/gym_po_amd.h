@@ -598,6 +598,43 @@ int gp_rollout_belief(gp_env* env, int K, void* obs, int32_t* actions, int32_t* 
 int gp_belief_backup(gp_env* env, int n_points, const float* points, int n_vectors, const float* alpha, float gamma,
                      float* alpha_out, int32_t* act_out, float* value_out, void* stream);
 
+/* ---- belief-set expansion (POMDP only; every other kind: GP_E_UNSUPPORTED) ----
+ * The other half of point-based value iteration (Pineau, Gordon & Thrun 2003): for every belief point the successor
+ * under the filter that lies farthest, in L1, from a reference set. Build-defined; pinned bit for bit to the numpy
+ * restatement tests/expand_oracle.py. The float laws Tf, Zf, terminal and the arithmetic are the filter's (above):
+ * float32, every product, difference, quotient and sum rounded separately (no FMA), sums sequential in ascending index
+ * from +0, the first maximiser wins (replaced only on a strict >).
+ * Rule. Points b[P][S] and a reference set q[Q][S] (NULL: the points themselves, Q = P) are finite and >= 0 and are
+ * used as given, not normalised. For every point, action a and obs o:
+ *   1. acc_a(s') = sum_s fl(b[s] Tf[s][a][s'])                                   (the backup's step 1)
+ *   2. u(s') = terminal[s'] ? +0 : fl(Zf[a][s'][o] acc_a(s')); n(a, o) = sum_s' u(s'). The candidate (a, o) is live
+ *      iff n > 0 and n is finite; its successor is b'(s') = fl(u(s') / n): the filter step of a step that did not
+ *      end, so a live successor is the filter's belief bit for bit. Successors through an episode end are no
+ *      candidates (they are the reset beliefs, which depend on no point).
+ *   3. dist(a, o) = min over q of L1(b', q), L1 = sum_s |fl(b'[s] - q[s])|, s ascending from +0. All values are finite
+ *      and >= 0, so the minimum is exact whatever its order.
+ *   4. (a*, o*) = the first live candidate of the largest dist, a ascending, then o ascending.
+ * Outputs per point: succ = b' of (a*, o*), dist, act = a*, obs = o*, mass = n(a*, o*). A point without a live
+ * candidate: act = obs = -1, dist = mass = +0, a row of +0.
+ * The device skips the terms of n with Zf == 0 and those at a terminal s' (u >= 0 and the accumulator starts at +0:
+ * the bits of the dense loop); the L1 sums are dense.
+ *
+ * gp_belief_expand: points float [P][S], ref float [Q][S] or NULL (device), succ_out float [P][S], dist_out float [P],
+ *   act_out / obs_out int32 [P], mass_out float [P] (device; each may be NULL). Asynchronous on `stream`: nothing is
+ *   copied or waited for unless the scratch grows. Reads the model and writes only its outputs: beliefs, env state,
+ *   step counter, metrics, an installed policy and the backup's results are untouched. P = 0 is a no-op.
+ *   GP_E_STATE without an enabled filter. GP_E_INVALID, naming the fault: P < 0 or P > 2^20, with ref given Q < 1 or
+ *   Q > 2^20, a scratch of 4 P A S + 4 P A O + 8 P A + 4 S Q bytes above 2^30, or P > 0 without points.
+ *   The scratch (acc [P][A][S], shared with gp_belief_backup; n [P][A][O]; per (p, a) the best (dist, o); the reference
+ *   set transposed [S][Q]) is owned by the handle, grows to the largest call seen and is freed by gp_belief_disable /
+ *   gp_destroy; the (a, o) lists of Zf are the backup's tables. gp_query: "expand_scratch_bytes" (acc included).
+ *   One stream per handle for the calls that share this scratch: gp_belief_expand and gp_belief_backup of one handle
+ *   write the same acc, and a gp_belief_backup that grows it waits only for its own stream before it frees the old one.
+ *   Queue them on one stream (or order the streams with events and let no call grow the scratch under another's
+ *   queued work); calls of different handles share nothing. */
+int gp_belief_expand(gp_env* env, int n_points, const float* points, int n_ref, const float* ref, float* succ_out,
+                     float* dist_out, int32_t* act_out, int32_t* obs_out, float* mass_out, void* stream);
+
 /* Canonical state (device pointers, int32 unless noted). GRID: agent cell, goal cell, elapsed
  * [B] each. TAXI: s, elapsed, n_dropoffs. CROOMS: agent yx f64[B,2], goal cell yx i32[B,2],
  * velocity f64[B,2], elapsed i32[B]. ANTTAG: agent cell, target cell, elapsed. ROCKSAMPLE: agent cell, good
